@@ -1,7 +1,15 @@
 """Benchmark: edges/s forward+backward (one training step) of the geometric message-passing hot
 path on MI355X (BASELINE.json metric).
 
-Default (--workload egnn+mace): the two halves of the metric in one run, one JSON line.
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) does only what the headline figure
+needs: it builds the graph and the first --workload's model (default EGNN, config C2), warms up,
+times the K steps, writes that step's outputs if --dump-outputs DIR is given and prints the JSON
+line (`value`, `ms_per_step`, and the roofline fields read from the HIP events of the timed steps
+themselves).  Everything that takes runs of its own is behind --full: the other workloads of
+--workload as secondary objects of the line, the egnn_f32_exact leg, the forward-only timing and
+the CPU baselines (each still with its own --no-... switch).
+
+--full (--workload egnn+mace+gvp+tfn): all halves of the metric in one run, one JSON line.
 `value` is config C2 — EGNN 4 layers, emb_dim 128, one seeded random 3-D radius graph with
 50,000 nodes and ~1M directed edges (r = 5, box tuned), synthetic data, random-init weights;
 the line's "mace" object is config C4 on the same graph (MACE L_max=2, correlation 3, 128
@@ -14,7 +22,8 @@ accumulated at the end of the backward pass).  Weak scaling: every rank owns its
 graph (seed = rank); gradients are averaged with one flat all-reduce per step (RCCL over
 xGMI).  --graph replays the step from a HIP graph instead of launching it eagerly.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py --full [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline]
     torchrun --nproc-per-node N bench.py --gpus N ...
 
 `python bench.py --gpus N` (N > 1) without torchrun's environment starts the N rank processes
@@ -60,9 +69,18 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the secondary "
+                         "workloads of --workload, the egnn_f32_exact leg, the forward-only "
+                         "timing and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step of the headline "
+                         "workload computed (rank 0: prediction, loss, parameter gradients and "
+                         "the parameters after the Adam step) as DIR/<name>.npy, float32, at "
+                         "most 64 MB in all")
     ap.add_argument("--workload", default="egnn+mace+gvp+tfn",
                     help="'+'-joined workloads (egnn, mace, gvp, tfn, schnet); the first is the "
-                         "line's value, the others its secondary objects")
+                         "line's value, the others its secondary objects (run under --full only)")
     ap.add_argument("--mace-steps", type=int, default=3,
                     help="timed steps of the secondary MACE / TFN workloads")
     ap.add_argument("--mace-warmup", type=int, default=1)
@@ -508,12 +526,40 @@ def mace_roofline(model, n_nodes, n_edges, timers, counts, n_steps, workload="ma
     return roof
 
 
+DUMP_BUDGET_BYTES = 48 << 20  # --dump-outputs: all files together stay well under 64 MB
+
+
+def dump_outputs(out_dir, pred, loss, model):
+    """--dump-outputs: what a caller of the timed step receives after its last step -- the model's
+    prediction, the loss, every parameter's gradient and the parameters after the optimizer step
+    -- as <out_dir>/<name>.npy (float32).  When the arrays together exceed DUMP_BUDGET_BYTES,
+    each array longer than an equal share keeps a fixed, seeded sample of its flattened elements
+    (ascending indices from numpy's default_rng(0)), the same from run to run."""
+    import numpy as np
+    arrays = {"pred": pred, "loss": loss}
+    for name, p in model.named_parameters():
+        if p.grad is not None:
+            arrays[f"grad.{name}"] = p.grad
+        arrays[f"param.{name}"] = p
+    arrays = {k: v.detach().to(torch.float32).cpu().numpy() for k, v in arrays.items()}
+    cap = None
+    if sum(a.nbytes for a in arrays.values()) > DUMP_BUDGET_BYTES:
+        cap = DUMP_BUDGET_BYTES // 4 // len(arrays)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if cap is not None and a.size > cap:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=cap, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 TIMER_NAMES = {"egnn": {"egnn_edge_fwd", "egnn_edge_bwd"}, "gvp": set(), "schnet": set()}
 
 
-def run_workload(workload, args, g, rank, world, dev, steps, warmup, exact=False):
+def run_workload(workload, args, g, rank, world, dev, steps, warmup, exact=False, dump_dir=None):
     """Build the model, warm up, time `steps` steps (barrier + synchronize on both sides, max
-    over ranks); returns the bench record fields of this workload (rank 0) or None."""
+    over ranks); returns the bench record fields of this workload (rank 0) or None.  dump_dir:
+    rank 0 writes the last timed step's outputs there (dump_outputs)."""
     import gmp_amd
     from gmp_amd import dist as gdist
     from gmp_amd import ops
@@ -536,8 +582,10 @@ def run_workload(workload, args, g, rank, world, dev, steps, warmup, exact=False
     def loss_fn():
         if args.fresh_graph:  # a new tensor object: the CSR caches miss, K0 runs every step
             batch.edge_index = batch.edge_index.clone()
-        return torch.nn.functional.l1_loss(model(batch).view(-1), y, reduction="sum")
+        last["pred"] = pred = model(batch)
+        return torch.nn.functional.l1_loss(pred.view(-1), y, reduction="sum")
 
+    last = {}  # the newest step's prediction (graph replay: the captured, static tensor)
     step = GraphedStep(model, loss_fn, opt, warmup=warmup, use_graph=args.graph)
     # only the regions the roofline reads are timed inside the measured steps
     ops.KERNEL_TIMER_NAMES = TIMER_NAMES.get(workload)
@@ -551,6 +599,8 @@ def run_workload(workload, args, g, rank, world, dev, steps, warmup, exact=False
     elapsed = time.perf_counter() - t0
     elapsed = gdist.max_over_ranks(elapsed, dev)
     total_edges = gdist.sum_over_ranks(g.num_edges, dev)
+    if dump_dir is not None and rank == 0:
+        dump_outputs(dump_dir, last["pred"], step.loss, model)
     if args.graph:
         # graph replays carry no per-kernel events: time the same kernels in a few eager steps
         ops.KERNEL_TIMERS = {}
@@ -577,7 +627,7 @@ def run_workload(workload, args, g, rank, world, dev, steps, warmup, exact=False
         torch.cuda.empty_cache()
         return rec
     fwd = None
-    if not args.no_forward:
+    if args.full and not args.no_forward:
         ops.KERNEL_TIMER_NAMES = None
         dt, ftimers = time_forward(model, batch, 1 if workload in ("mace", "tfn") else 5)
         fwd = forward_roofline(workload, model, g, layers, dt, ftimers)
@@ -735,7 +785,11 @@ def main():
     if args.plumbing:
         run_plumbing(args)
         return
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
     names = args.workload.split("+")
+    if not args.full:  # a plain run times the headline workload only
+        names = names[:1]
     for w in names:
         if w not in WORKLOADS:
             raise SystemExit(f"bench.py: unknown workload {w!r} (choices: {', '.join(WORKLOADS)})")
@@ -763,9 +817,10 @@ def main():
             warmup = max(1, min(args.warmup, args.mace_warmup))
         else:
             steps, warmup = min(args.steps, 10), max(1, min(args.warmup, 2))
-        recs[w] = run_workload(w, args, g, rank, world, dev, steps, warmup)
+        recs[w] = run_workload(w, args, g, rank, world, dev, steps, warmup,
+                               dump_dir=args.dump_outputs if k == 0 else None)
     exact = None
-    if names[0] == "egnn" and not args.no_f32_exact:
+    if args.full and names[0] == "egnn" and not args.no_f32_exact:
         exact = run_workload("egnn", args, g, rank, world, dev, min(args.steps, 5),
                              max(1, min(args.warmup, 2)), exact=True)
     if rank == 0:
@@ -803,7 +858,7 @@ def main():
         rec["forward"] = main_rec.get("forward")
         for w in names[1:]:
             rec[w] = {k: v for k, v in recs[w].items()}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline(g, args, names[0])
             for w in names[1:]:
                 rec[w]["cpu_baseline"] = cpu_baseline(g, args, w)

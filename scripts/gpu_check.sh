@@ -3,15 +3,16 @@
 # first failure.
 set -o pipefail
 cd "$GRAFT_REPO_ROOT"
-mkdir -p gpurun_out
+OUT=${OUT:-bench_out}  # where this script leaves its logs
+mkdir -p "$OUT"
 export TMPDIR=/tmp
-timeout -k 10 1000 python -u -m pytest tests -v -m gpu --timeout 300 --timeout-method thread > gpurun_out/pytest_gpu.log 2>&1
+timeout -k 10 1000 python -u -m pytest tests -v -m gpu --timeout 300 --timeout-method thread > "$OUT"/pytest_gpu.log 2>&1
 rc=$?
-echo "pytest rc=$rc" >> gpurun_out/pytest_gpu.log
+echo "pytest rc=$rc" >> "$OUT"/pytest_gpu.log
 if [ $rc -ne 0 ]; then exit $rc; fi
-timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1 || exit $?
-timeout -k 10 600 python bench.py > gpurun_out/bench.log 2>&1 || exit $?
+timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT"/smoke.log 2>&1 || exit $?
+timeout -k 10 600 python bench.py --full > "$OUT"/bench.log 2>&1 || exit $?
 if [ "${PROFILE:-0}" = "1" ]; then
-  mkdir -p gpurun_out/prof
-  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof -o egnn -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline > gpurun_out/prof_bench.log 2>&1
+  mkdir -p "$OUT"/prof
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT"/prof -o egnn -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > "$OUT"/prof_bench.log 2>&1
 fi
