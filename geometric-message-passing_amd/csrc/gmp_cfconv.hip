@@ -116,6 +116,46 @@ __global__ __launch_bounds__(256) void cfconv_wgrad(
   }
 }
 
+// dc[e] = sum_f g[gidx[e], f] * x[xidx[e], f] * w[e, f] (* s[e]): the gradient w.r.t. the per-edge
+// factor C of the scaled forms (and, with arguments substituted, every second-order term of
+// CFConv that ends on an (E) array).  pow2_at_least(cpr) lanes own one edge (the grouping of
+// cfconv_gather_mul_sum), 64 / lpr edges per wave at a time; each lane sums its float4 columns
+// in ascending order, then the group reduces by xor shuffles in a fixed order: deterministic, no
+// atomics.  w is the only E-sized stream (read once); the node rows come from L2.
+template <bool SCALED>
+__global__ __launch_bounds__(256) void cfconv_cgrad(
+    const float4* __restrict__ g, int64_t n_g, const int64_t* __restrict__ gidx,
+    const float4* __restrict__ x, int64_t n_x, const int64_t* __restrict__ xidx,
+    const float4* __restrict__ w, const float* __restrict__ es, int64_t n_items, int64_t cpr,
+    float* __restrict__ dc, int32_t* __restrict__ err) {
+  const int lane = threadIdx.x & 63;
+  const int lpr = pow2_at_least(cpr);
+  const int R = 64 / lpr, sub = lane / lpr, l = lane % lpr;
+  const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
+  const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  for (int64_t e0 = wave * R; e0 < n_items; e0 += n_waves * R) {  // e0 is wave-uniform
+    const int64_t e = e0 + sub;
+    const bool live = e < n_items;
+    float s = 0.f;
+    if (live) {
+      const int64_t a = gidx[e], b = xidx[e];
+      if (a >= 0 && a < n_g && b >= 0 && b < n_x) {
+        for (int64_t c = l; c < cpr; c += lpr) {
+          const float4 p = g[a * cpr + c], q = x[b * cpr + c], r = w[e * cpr + c];
+          s = fmaf(p.x * q.x, r.x, s);
+          s = fmaf(p.y * q.y, r.y, s);
+          s = fmaf(p.z * q.z, r.z, s);
+          s = fmaf(p.w * q.w, r.w, s);
+        }
+      } else if (l == 0) {
+        *err = 1;
+      }
+    }
+    for (int off = 1; off < lpr; off <<= 1) s += __shfl_xor(s, off);
+    if (live && l == 0) dc[e] = SCALED ? s * es[e] : s;
+  }
+}
+
 bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 
 }  // namespace
@@ -180,6 +220,29 @@ int gmp_cfconv_wgrad_f32(const float* g, int64_t n_g, const int64_t* gidx, const
                          int32_t* err, void* stream) {
   return gmp_cfconv_wgrad_scaled_f32(g, n_g, gidx, x, n_x, xidx, nullptr, n_items, F, dw, err,
                                      stream);
+}
+
+int gmp_cfconv_cgrad_f32(const float* g, int64_t n_g, const int64_t* gidx, const float* x,
+                         int64_t n_x, const int64_t* xidx, const float* w, const float* escale,
+                         int64_t n_items, int64_t F, float* dc, int32_t* err, void* stream) {
+  GMP_CHECK_ARG(n_g >= 0 && n_x >= 0 && n_items >= 0 && F >= 0);
+  if (n_items == 0) return GMP_OK;
+  GMP_CHECK_ARG(F > 0 && F % 4 == 0 && g && gidx && x && xidx && w && dc && err);
+  GMP_CHECK_ARG(aligned16(g) && aligned16(x) && aligned16(w));
+  const int64_t cpr = F / 4;
+  int lpr = 1;
+  while (lpr < cpr && lpr < 64) lpr <<= 1;
+  const int64_t per_block = 4 * (64 / lpr);  // edges per 256-thread block and pass
+  const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(n_items, per_block), 256 * 64);
+  if (escale)
+    cfconv_cgrad<true><<<grid, 256, 0, as_stream(stream)>>>(
+        reinterpret_cast<const float4*>(g), n_g, gidx, reinterpret_cast<const float4*>(x), n_x,
+        xidx, reinterpret_cast<const float4*>(w), escale, n_items, cpr, dc, err);
+  else
+    cfconv_cgrad<false><<<grid, 256, 0, as_stream(stream)>>>(
+        reinterpret_cast<const float4*>(g), n_g, gidx, reinterpret_cast<const float4*>(x), n_x,
+        xidx, reinterpret_cast<const float4*>(w), nullptr, n_items, cpr, dc, err);
+  return launch_status();
 }
 
 }  // extern "C"

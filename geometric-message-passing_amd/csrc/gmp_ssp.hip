@@ -43,6 +43,34 @@ __global__ __launch_bounds__(256) void ssp_bwd(const float4* __restrict__ x,
   }
 }
 
+// Second order: the backward dx = g * sigmoid(x) differentiated once more.  With the cotangent a
+// of dx:  gg = a * sigmoid(x) (the same form as ssp1_bwd) and gx = a * g * sigmoid'(x), where
+// sigmoid'(x) = e / (1 + e)^2 with e = exp(-|x|) in (0, 1]: no overflow, and it underflows to 0
+// for large |x| (finite everywhere).
+__device__ __forceinline__ void ssp1_bwd2(float x, float g, float a, float& gg, float& gx) {
+  gg = a / (1.f + __expf(-x));
+  const float e = __expf(-fabsf(x));
+  const float r = 1.f / (1.f + e);
+  gx = a * g * (e * r * r);
+}
+
+__global__ __launch_bounds__(256) void ssp_bwd2(const float4* __restrict__ x,
+                                                const float4* __restrict__ g,
+                                                const float4* __restrict__ a, int64_t n4,
+                                                float4* __restrict__ gg, float4* __restrict__ gx) {
+  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n4;
+       t += (int64_t)gridDim.x * blockDim.x) {
+    const float4 v = x[t], w = g[t], c = a[t];
+    float4 og, ox;
+    ssp1_bwd2(v.x, w.x, c.x, og.x, ox.x);
+    ssp1_bwd2(v.y, w.y, c.y, og.y, ox.y);
+    ssp1_bwd2(v.z, w.z, c.z, og.z, ox.z);
+    ssp1_bwd2(v.w, w.w, c.w, og.w, ox.w);
+    gg[t] = og;
+    gx[t] = ox;
+  }
+}
+
 bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 
 unsigned grid_for4(int64_t n4) {
@@ -74,6 +102,19 @@ int gmp_ssp_bwd_f32(const float* x, const float* grad_y, int64_t n, float* grad_
   ssp_bwd<<<grid_for4(n / 4), 256, 0, as_stream(stream)>>>(
       reinterpret_cast<const float4*>(x), reinterpret_cast<const float4*>(grad_y), n / 4,
       reinterpret_cast<float4*>(grad_x));
+  return launch_status();
+}
+
+int gmp_ssp_bwd2_f32(const float* x, const float* grad_y, const float* a, int64_t n, float* gg,
+                     float* gx, void* stream) {
+  GMP_CHECK_ARG(n >= 0);
+  if (n == 0) return GMP_OK;
+  GMP_CHECK_ARG(x && grad_y && a && gg && gx && n % 4 == 0 && aligned16(x) &&
+                aligned16(grad_y) && aligned16(a) && aligned16(gg) && aligned16(gx));
+  ssp_bwd2<<<grid_for4(n / 4), 256, 0, as_stream(stream)>>>(
+      reinterpret_cast<const float4*>(x), reinterpret_cast<const float4*>(grad_y),
+      reinterpret_cast<const float4*>(a), n / 4, reinterpret_cast<float4*>(gg),
+      reinterpret_cast<float4*>(gx));
   return launch_status();
 }
 

@@ -421,6 +421,46 @@ Tensor ssp_bwd(const Tensor& x, const Tensor& gy) {
   return gx;
 }
 
+// (dc (E), err (1) int32): err != 0 when a gather index was out of range (its dc is 0)
+std::tuple<Tensor, Tensor> cfconv_cgrad(const Tensor& gr, const Tensor& gidx, const Tensor& x,
+                                        const Tensor& xidx, const Tensor& w,
+                                        const optional<Tensor>& escale) {
+  OpGuard g(gr, "cfconv_cgrad");
+  f32(gr, "g");
+  f32(x, "x");
+  f32(w, "w");
+  i64(gidx, "gidx");
+  i64(xidx, "xidx");
+  TORCH_CHECK(gr.dim() == 2 && x.dim() == 2 && w.dim() == 2 && gr.size(1) == x.size(1) &&
+                  w.size(1) == x.size(1),
+              "gmp.cfconv_cgrad: g (N, F), x (N, F), w (E, F)");
+  const int64_t E = w.size(0);
+  numel(gidx, E, "gidx");
+  numel(xidx, E, "xidx");
+  opt_f32(escale, {E}, "escale");
+  Tensor dc = at::empty({E}, x.options());
+  Tensor err = at::zeros({1}, x.options().dtype(at::kInt));
+  check_rc(gmp_cfconv_cgrad_f32(fp(gr), gr.size(0), ip(gidx), fp(x), x.size(0), ip(xidx), fp(w),
+                                cfp(escale), E, x.size(1), fp(dc), err.data_ptr<int32_t>(),
+                                cur_stream()),
+           "gmp_cfconv_cgrad_f32");
+  return {dc, err};
+}
+
+// (gg, gx): cotangents of grad_y and x for the cotangent a of ssp_bwd's output
+std::tuple<Tensor, Tensor> ssp_bwd2(const Tensor& x, const Tensor& gy, const Tensor& a) {
+  OpGuard g(x, "ssp_bwd2");
+  f32(x, "x");
+  f32(gy, "grad_y");
+  f32(a, "a");
+  shape(gy, x.sizes(), "grad_y");
+  shape(a, x.sizes(), "a");
+  Tensor gg = at::empty_like(x), gx = at::empty_like(x);
+  check_rc(gmp_ssp_bwd2_f32(fp(x), fp(gy), fp(a), x.numel(), fp(gg), fp(gx), cur_stream()),
+           "gmp_ssp_bwd2_f32");
+  return {gg, gx};
+}
+
 // ------------------------------------------------------------------ LayerNorm + activation rows
 std::tuple<Tensor, Tensor, Tensor> ln_act_fwd(const Tensor& x, const Tensor& gamma,
                                               const Tensor& beta, double eps, int64_t act) {
@@ -612,6 +652,33 @@ Tensor schnet_featurize_bwd(const Tensor& pos, const Tensor& edge_index, const T
                                         cfp(g_cut), fp(gv), cur_stream()),
            "gmp_schnet_featurize_bwd_f32");
   return gv;
+}
+
+// (gg_dist (E), gg_rbf (E, G), gg_cut (E), h_vec (E, 3)); an output not wanted is a 0-element
+// tensor and its kernel path is skipped.
+std::tuple<Tensor, Tensor, Tensor, Tensor> schnet_featurize_bwd2(
+    const Tensor& pos, const Tensor& edge_index, const Tensor& offsets, double coeff,
+    double cutoff, const optional<Tensor>& g_dist, const optional<Tensor>& g_rbf,
+    const optional<Tensor>& g_cut, const Tensor& a_vec, bool want_dist, bool want_rbf,
+    bool want_cut, bool want_vec) {
+  OpGuard g(pos, "schnet_featurize_bwd2");
+  const int64_t E = edge_checks(pos, edge_index);
+  f32(offsets, "offsets");
+  f32(a_vec, "a_vec");
+  const int64_t G = offsets.numel();
+  opt_f32(g_dist, {E}, "g_dist");
+  opt_f32(g_rbf, {E, G}, "g_rbf");
+  opt_f32(g_cut, {E}, "g_cut");
+  shape(a_vec, {E, 3}, "a_vec");
+  auto o = pos.options();
+  Tensor gd = at::empty({want_dist ? E : 0}, o), gr = at::empty({want_rbf ? E : 0, G}, o),
+         gc = at::empty({want_cut ? E : 0}, o), hv = at::empty({want_vec ? E : 0, 3}, o);
+  check_rc(gmp_schnet_featurize_bwd2_f32(fp(pos), pos.size(0), ip(edge_index), E, (int)G,
+                                         fp(offsets), (float)coeff, (float)cutoff, cfp(g_dist),
+                                         cfp(g_rbf), cfp(g_cut), fp(a_vec), fp(gd), fp(gr), fp(gc),
+                                         fp(hv), cur_stream()),
+           "gmp_schnet_featurize_bwd2_f32");
+  return {gd, gr, gc, hv};
 }
 
 // ------------------------------------------------------------------ K16 Gate / BatchNorm
@@ -1627,6 +1694,13 @@ Tensor cfconv_wgrad(const Tensor&, const Tensor& gidx, const Tensor& x, const Te
 }
 Tensor ssp_fwd(const Tensor& x, double) { return at::empty_like(x); }
 Tensor ssp_bwd(const Tensor& x, const Tensor&) { return at::empty_like(x); }
+std::tuple<Tensor, Tensor> cfconv_cgrad(const Tensor&, const Tensor&, const Tensor& x,
+                                        const Tensor&, const Tensor& w, const optional<Tensor>&) {
+  return {at::empty({w.size(0)}, x.options()), at::empty({1}, x.options().dtype(at::kInt))};
+}
+std::tuple<Tensor, Tensor> ssp_bwd2(const Tensor& x, const Tensor&, const Tensor&) {
+  return {at::empty_like(x), at::empty_like(x)};
+}
 std::tuple<Tensor, Tensor, Tensor> ln_act_fwd(const Tensor& x, const Tensor&, const Tensor&, double,
                                               int64_t) {
   return {at::empty_like(x), at::empty_like(x), at::empty({x.numel() / x.size(-1)}, x.options())};
@@ -1672,6 +1746,15 @@ Tensor schnet_featurize_bwd(const Tensor& pos, const Tensor& ei, const Tensor&, 
                             const optional<Tensor>&, const optional<Tensor>&,
                             const optional<Tensor>&) {
   return at::empty({ei.size(1), 3}, pos.options());
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor> schnet_featurize_bwd2(
+    const Tensor& pos, const Tensor& ei, const Tensor& offsets, double, double,
+    const optional<Tensor>&, const optional<Tensor>&, const optional<Tensor>&, const Tensor&,
+    bool want_dist, bool want_rbf, bool want_cut, bool want_vec) {
+  const int64_t E = ei.size(1);
+  auto o = pos.options();
+  return {at::empty({want_dist ? E : 0}, o), at::empty({want_rbf ? E : 0, offsets.numel()}, o),
+          at::empty({want_cut ? E : 0}, o), at::empty({want_vec ? E : 0, 3}, o)};
 }
 Tensor gate_fwd(const Tensor& x, const Tensor& out_map, double, double) {
   return at::empty({x.size(0), out_map.size(0)}, x.options());
@@ -1863,6 +1946,9 @@ TORCH_LIBRARY(gmp, m) {
         "Tensor");
   m.def("ssp_fwd(Tensor x, float shift) -> Tensor");
   m.def("ssp_bwd(Tensor x, Tensor grad_y) -> Tensor");
+  m.def("cfconv_cgrad(Tensor g, Tensor gidx, Tensor x, Tensor xidx, Tensor w, "
+        "Tensor? escale=None) -> (Tensor dc, Tensor err)");
+  m.def("ssp_bwd2(Tensor x, Tensor grad_y, Tensor a) -> (Tensor gg, Tensor gx)");
   m.def("ln_act_fwd(Tensor x, Tensor gamma, Tensor beta, float eps, int act) -> "
         "(Tensor y, Tensor xhat, Tensor rstd)");
   m.def("ln_act_bwd(Tensor grad_y, Tensor xhat, Tensor rstd, Tensor gamma, Tensor beta, "
@@ -1884,6 +1970,10 @@ TORCH_LIBRARY(gmp, m) {
         "float cutoff) -> (Tensor dist, Tensor rbf, Tensor cut)");
   m.def("schnet_featurize_bwd(Tensor pos, Tensor edge_index, Tensor offsets, float coeff, "
         "float cutoff, Tensor? g_dist, Tensor? g_rbf, Tensor? g_cut) -> Tensor");
+  m.def("schnet_featurize_bwd2(Tensor pos, Tensor edge_index, Tensor offsets, float coeff, "
+        "float cutoff, Tensor? g_dist, Tensor? g_rbf, Tensor? g_cut, Tensor a_vec, "
+        "bool want_dist=True, bool want_rbf=True, bool want_cut=True, bool want_vec=True) -> "
+        "(Tensor gg_dist, Tensor gg_rbf, Tensor gg_cut, Tensor h_vec)");
   m.def("gate_fwd(Tensor x, Tensor out_map, float c_act, float c_gate) -> Tensor");
   m.def("gate_bwd(Tensor x, Tensor grad_y, Tensor in_map, float c_act, float c_gate) -> Tensor");
   m.def("irreps_bn_fwd(Tensor x, Tensor col_chan, Tensor chan_col, Tensor chan_info, "
@@ -1962,6 +2052,8 @@ TORCH_LIBRARY(gmp, m) {
   m.impl("cfconv_wgrad", ns cfconv_wgrad);                                \
   m.impl("ssp_fwd", ns ssp_fwd);                                          \
   m.impl("ssp_bwd", ns ssp_bwd);                                          \
+  m.impl("cfconv_cgrad", ns cfconv_cgrad);                                \
+  m.impl("ssp_bwd2", ns ssp_bwd2);                                        \
   m.impl("ln_act_fwd", ns ln_act_fwd);                                    \
   m.impl("ln_act_bwd", ns ln_act_bwd);                                    \
   m.impl("edge_xyz_dot", ns edge_xyz_dot);                                \
@@ -1977,6 +2069,7 @@ TORCH_LIBRARY(gmp, m) {
   m.impl("edge_featurize_gvp_bwd", ns edge_featurize_gvp_bwd);            \
   m.impl("schnet_featurize", ns schnet_featurize);                        \
   m.impl("schnet_featurize_bwd", ns schnet_featurize_bwd);                \
+  m.impl("schnet_featurize_bwd2", ns schnet_featurize_bwd2);              \
   m.impl("gate_fwd", ns gate_fwd);                                        \
   m.impl("gate_bwd", ns gate_bwd);                                        \
   m.impl("irreps_bn_fwd", ns irreps_bn_fwd);                              \

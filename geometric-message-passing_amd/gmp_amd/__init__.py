@@ -15,10 +15,13 @@ from .equivariant import (TensorProductConvLayer, MACEModel, TFNModel,  # noqa: 
                           SymmetricContraction, first_node_pooling)
 from .gvp import GVP, GVPConv, GVPConvLayer, GVPGNNModel  # noqa: F401
 from .schnet import SchNetModel, CFConv, InteractionBlock  # noqa: F401
+from .ops import second_order  # noqa: F401
+from .forces import energy_and_forces  # noqa: F401
 
 __all__ = ["scatter", "scatter_sum", "scatter_add", "scatter_mean", "scatter_max", "scatter_min",
            "global_add_pool", "global_mean_pool", "MessagePassing", "EGNNLayer", "EGNNModel",
            "Batch", "collate", "radius_graph", "create_kchains", "TensorProductConvLayer",
            "MACEModel", "TFNModel", "RadialEmbeddingBlock", "EquivariantProductBasisBlock",
            "SymmetricContraction", "first_node_pooling", "GVP", "GVPConv", "GVPConvLayer",
-           "GVPGNNModel", "SchNetModel", "CFConv", "InteractionBlock"]
+           "GVPGNNModel", "SchNetModel", "CFConv", "InteractionBlock", "second_order",
+           "energy_and_forces"]

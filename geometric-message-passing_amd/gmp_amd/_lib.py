@@ -204,6 +204,12 @@ SIGNATURES = {
     "gmp_egnn_edge_bwd_f32": (c_int, [c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp,
                                       ctypes.POINTER(GmpEgnnParams), c_int, c_int, c_vp, c_int]
                               + [c_vp] * 11),
+    # second-order (energy-and-force) kernels; additions only, the ABI version is unchanged
+    "gmp_cfconv_cgrad_f32": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64,
+                                     c_i64, c_vp, c_vp, c_vp]),
+    "gmp_ssp_bwd2_f32": (c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "gmp_schnet_featurize_bwd2_f32": (c_int, [c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_f32, c_f32]
+                                      + [c_vp] * 9),
 }
 
 # include/gmp.h GMP_ABI_VERSION (6: r06 — K17 gmp_gvp_ff_{fwd,bwd}_f32, K15b gmp_egnn_node_bwd_f32;

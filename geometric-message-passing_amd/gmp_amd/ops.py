@@ -479,7 +479,8 @@ def linear(x, W, b=None):
     shp = x.shape
     x2 = x.reshape(-1, shp[-1])
     if x2.is_cuda and x2.shape[0] >= EDGE_LINEAR_MIN_ROWS and x2.dtype == torch.float32:
-        y = EdgeLinearFn.apply(x2.contiguous(), W, b)
+        fn = EdgeLinear2Fn if _SECOND_ORDER[0] else EdgeLinearFn
+        y = fn.apply(x2.contiguous(), W, b)
     else:
         y = torch.nn.functional.linear(x2, W, b)
     return y.reshape(shp[:-1] + (W.shape[0],))
@@ -551,7 +552,7 @@ def gather(src, index, dim=0):
     x = src.movedim(dim, 0)
     shp = x.shape
     x2 = x.reshape(shp[0], -1)
-    out = GatherRowsFn.apply(x2, index, shp[0])
+    out = (GatherRows2Fn if _SECOND_ORDER[0] else GatherRowsFn).apply(x2, index, shp[0])
     return out.reshape((index.numel(),) + tuple(shp[1:])).movedim(0, dim)
 
 
@@ -634,14 +635,19 @@ def shifted_softplus(x, shift):
     """F.softplus(x) - shift through K14 (CUDA fp32, numel % 4 == 0, 16-byte aligned)."""
     x = _f32c(x)
     _need_cuda(x)
-    return ShiftedSoftplusFn.apply(x, shift)
+    return (ShiftedSoftplus2Fn if _SECOND_ORDER[0] else ShiftedSoftplusFn).apply(x, shift)
 
 
 def cfconv_propagate(edge_index, x, W, C=None):
     """sum_{e: dst[e] = i} x[src[e]] * W[e] (* C[e]) for edge_index = (src, dst), N =
-    x.shape[0]; C (E,) is a per-edge factor without gradient (SchNet's cosine cutoff)."""
+    x.shape[0]; C (E,) is a per-edge factor without gradient (SchNet's cosine cutoff).  Inside
+    second_order() the twice-differentiable form is recorded and C may require grad."""
     x, W = _f32c(x), _f32c(W)
     _need_cuda(x, W)
+    if _SECOND_ORDER[0]:
+        ei = _i64c(edge_index)
+        return cfconv_receiver_aggregate(x, W, None if C is None else C.reshape(-1), ei[0],
+                                         ei[1], x.shape[0])
     if C is not None:
         if C.requires_grad and torch.is_grad_enabled():
             raise ValueError("cfconv_propagate: C must not require grad")
@@ -949,3 +955,377 @@ class EgnnNodeFn(torch.autograd.Function):
         return ((dh, dm) + sw.deliver(ctx.needs_input_grad, 2,
                                       (W0, b0, ln1w, ln1b, W3, b3, ln2w, ln2b), grads)
                 + (None, None, None, None, None, None))
+
+
+# ----------------------------------------------------------------------------------- 2nd order
+# Energy-and-force training (F = -dE/dpos, a loss on F) differentiates the backward pass once
+# more.  Inside `with second_order():` the SchNet path records the Functions below instead of the
+# once-differentiable ones above: each backward is itself a Function (or plain torch ops), so
+# torch.autograd.grad(E, pos, create_graph=True) builds a graph that loss.backward() can walk.
+# Outside the context nothing changes.  The other models' Functions stay once-differentiable in
+# either state: a second-order backward through them raises.
+_SECOND_ORDER = [False]
+
+
+def second_order_enabled():
+    return _SECOND_ORDER[0]
+
+
+class second_order:
+    """Context manager: record twice-differentiable Functions on the SchNet path (CFConv with a
+    differentiable cutoff, shifted softplus, the SchNet featurisation, segmented sum / mean,
+    gather, ops.linear).  The routing is decided when the forward runs; the backward calls may
+    come after the block has exited.  Nests; restores the previous state on exit."""
+
+    def __enter__(self):
+        if compiling():
+            raise NotImplementedError("gmp_amd.second_order() is not supported under "
+                                      "torch.compile tracing")
+        self.prev = _SECOND_ORDER[0]
+        _SECOND_ORDER[0] = True
+        return self
+
+    def __exit__(self, *exc):
+        _SECOND_ORDER[0] = self.prev
+        return False
+
+
+def _leaf_grad_unused(p):
+    """True when p is a leaf whose gradient the running backward pass neither accumulates nor
+    captures (torch.autograd.grad(E, pos): the parameters' AccumulateGrad nodes are not part of
+    the pass), so an E-sized weight-gradient reduction can be skipped.  The engine refuses the
+    query for a leaf that autograd.grad captures: then the gradient is wanted."""
+    if p is None or not p.is_leaf:
+        return False
+    try:
+        with torch.enable_grad():
+            acc = p.view_as(p).grad_fn.next_functions[0][0]
+        return not torch._C._will_engine_execute_node(acc)
+    except (RuntimeError, AttributeError, IndexError):
+        return False
+
+
+def _al16(t):
+    """Contiguous fp32 at a 16-byte aligned address (a contiguous view at an odd offset is
+    copied): what the float4 kernels need."""
+    t = _f32c(t)
+    return t.clone() if t.data_ptr() % 16 else t
+
+
+# CFConv is one multilinear form T(g, x, W, C) = sum_e C_e sum_f g[dst_e, f] x[src_e, f] W[e, f].
+# Its partial derivatives: over g the receiver aggregate, over x the sender aggregate (the same
+# kernel with the index roles swapped: CFAggFn), over W the per-edge product (CFEdgeProdFn), over
+# C the per-edge dot product (CFEdgeDotFn).  Every first- and second-order term is one of these
+# with arguments substituted, so each Function's backward calls the other two; higher orders
+# follow by composition.
+#
+# Every Function here saves the tensors it was GIVEN, never a contiguous / aligned copy made
+# inside forward(): such a copy is cut off from the graph, and a second-order gradient through it
+# would silently come out as zero.
+class CFAggFn(torch.autograd.Function):
+    """out[s] = sum_{e: sidx[e] = s} C[e] x[xidx[e]] * W[e] (K13 over the CSR of sidx); C may be
+    None.  The receiver aggregate is (xidx, sidx) = (src, dst), the sender aggregate (dst, src)."""
+
+    @staticmethod
+    def forward(ctx, x, W, C, xidx, sidx, n_seg):
+        ctx.save_for_backward(x, W, C)
+        ctx.xidx, ctx.sidx = xidx, sidx
+        return cfconv_aggregate(_al16(x), xidx, _al16(W), _cfconv_csr(sidx, n_seg),
+                                None if C is None else _f32c(C))
+
+    @staticmethod
+    def backward(ctx, a):
+        x, W, C = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dx = CFAggFn.apply(a, W, C, ctx.sidx, ctx.xidx, x.shape[0]) if need[0] else None
+        dW = CFEdgeProdFn.apply(a, x, C, ctx.sidx, ctx.xidx) if need[1] else None
+        dC = CFEdgeDotFn.apply(a, x, W, ctx.sidx, ctx.xidx) if C is not None and need[2] else None
+        return dx, dW, dC, None, None, None
+
+
+class CFEdgeProdFn(torch.autograd.Function):
+    """out[e] = C[e] g[gidx[e]] * x[xidx[e]] (gmp_cfconv_wgrad_scaled_f32); C may be None."""
+
+    @staticmethod
+    def forward(ctx, g, x, C, gidx, xidx):
+        ctx.save_for_backward(g, x, C)
+        ctx.gidx, ctx.xidx = gidx, xidx
+        return _lib.torch_ops().cfconv_wgrad(_al16(g), _i64c(gidx), _al16(x), _i64c(xidx),
+                                             None if C is None else _f32c(C))
+
+    @staticmethod
+    def backward(ctx, a):
+        g, x, C = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dg = CFAggFn.apply(x, a, C, ctx.xidx, ctx.gidx, g.shape[0]) if need[0] else None
+        dx = CFAggFn.apply(g, a, C, ctx.gidx, ctx.xidx, x.shape[0]) if need[1] else None
+        dC = CFEdgeDotFn.apply(g, x, a, ctx.gidx, ctx.xidx) if C is not None and need[2] else None
+        return dg, dx, dC, None, None
+
+
+class CFEdgeDotFn(torch.autograd.Function):
+    """out[e] = sum_f g[gidx[e], f] x[xidx[e], f] W[e, f] (gmp_cfconv_cgrad_f32)."""
+
+    @staticmethod
+    def forward(ctx, g, x, W, gidx, xidx):
+        ctx.save_for_backward(g, x, W)
+        ctx.gidx, ctx.xidx = gidx, xidx
+        return cfconv_cgrad(_al16(g), gidx, _al16(x), xidx, _al16(W))[0]
+
+    @staticmethod
+    def backward(ctx, a):
+        g, x, W = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dg = CFAggFn.apply(x, W, a, ctx.xidx, ctx.gidx, g.shape[0]) if need[0] else None
+        dx = CFAggFn.apply(g, W, a, ctx.gidx, ctx.xidx, x.shape[0]) if need[1] else None
+        dW = CFEdgeProdFn.apply(g, x, a, ctx.gidx, ctx.xidx) if need[2] else None
+        return dg, dx, dW, None, None
+
+
+def cfconv_cgrad(g, gidx, x, xidx, w, escale=None):
+    """(dc (E), err (1) int32) with dc[e] = sum_f g[gidx[e], f] x[xidx[e], f] w[e, f]
+    (* escale[e]) (gmp_cfconv_cgrad_f32); err != 0 when a gather index was out of range."""
+    g, x, w = _f32c(g), _f32c(x), _f32c(w)
+    _need_cuda(g, x, w)
+    return _lib.torch_ops().cfconv_cgrad(g, _i64c(gidx), x, _i64c(xidx), w, escale)
+
+
+def cfconv_receiver_aggregate(x, W, C, src, dst, n):
+    """dT/dg: out[i] = sum_{e: dst[e] = i} C[e] x[src[e]] * W[e] (the CFConv forward)."""
+    return CFAggFn.apply(x, W, C, src, dst, n)
+
+
+def cfconv_sender_aggregate(g, W, C, src, dst, n):
+    """dT/dx: out[j] = sum_{e: src[e] = j} C[e] g[dst[e]] * W[e]."""
+    return CFAggFn.apply(g, W, C, dst, src, n)
+
+
+def cfconv_edge_product(g, x, C, src, dst):
+    """dT/dW: out[e] = C[e] g[dst[e]] * x[src[e]]."""
+    return CFEdgeProdFn.apply(g, x, C, dst, src)
+
+
+def cfconv_edge_dot(g, x, W, src, dst):
+    """dT/dC: out[e] = sum_f g[dst[e], f] x[src[e], f] W[e, f]."""
+    return CFEdgeDotFn.apply(g, x, W, dst, src)
+
+
+class ShiftedSoftplus2Fn(torch.autograd.Function):
+    """ShiftedSoftplusFn whose backward is recorded (SspBwdFn)."""
+
+    @staticmethod
+    def forward(ctx, x, shift):
+        y = _lib.torch_ops().ssp_fwd(x, float(shift))
+        ctx.save_for_backward(x)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        (x,) = ctx.saved_tensors
+        return SspBwdFn.apply(x, g), None
+
+
+class SspBwdFn(torch.autograd.Function):
+    """dx = g * sigmoid(x) (gmp_ssp_bwd_f32); backward by gmp_ssp_bwd2_f32.  Force training needs
+    exactly two orders: the second backward is once-differentiable."""
+
+    @staticmethod
+    def forward(ctx, x, g):
+        ctx.save_for_backward(x, g)
+        return _lib.torch_ops().ssp_bwd(x, _al16(g))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, a):
+        x, g = ctx.saved_tensors
+        gg, gx = _lib.torch_ops().ssp_bwd2(x, _al16(g), _al16(a))
+        return gx, gg
+
+
+class EdgeVecToPosFn(torch.autograd.Function):
+    """edge_vec_to_pos_grad as a Function: linear in g_vec, its transpose is EdgePosDiffFn."""
+
+    @staticmethod
+    def forward(ctx, g_vec, edge_index, n):
+        ctx.ei, ctx.n = edge_index, n
+        return edge_vec_to_pos_grad(_f32c(g_vec), edge_index, n)
+
+    @staticmethod
+    def backward(ctx, a):
+        return EdgePosDiffFn.apply(a, ctx.ei), None, None
+
+
+class EdgePosDiffFn(torch.autograd.Function):
+    """a_pos[ei0] - a_pos[ei1] (the gather kernel); its transpose is EdgeVecToPosFn."""
+
+    @staticmethod
+    def forward(ctx, a_pos, edge_index):
+        ctx.ei, ctx.n = edge_index, a_pos.shape[0]
+        a_pos = _f32c(a_pos)
+        return gather_rows(a_pos, edge_index[0]) - gather_rows(a_pos, edge_index[1])
+
+    @staticmethod
+    def backward(ctx, g):
+        return EdgeVecToPosFn.apply(g, ctx.ei, ctx.n), None
+
+
+class SchNetFeaturize2Fn(torch.autograd.Function):
+    """SchNetFeaturizeFn whose backward is recorded (SchNetFeaturizeBwdFn, EdgeVecToPosFn)."""
+
+    @staticmethod
+    def forward(ctx, pos, edge_index, offsets, coeff, cutoff):
+        ei, off = _i64c(edge_index), _f32c(offsets)
+        _need_cuda(pos, ei, off)
+        with _timed("edge_featurize"):
+            d, rbf, cut = _lib.torch_ops().schnet_featurize(_f32c(pos), ei, off, float(coeff),
+                                                            float(cutoff))
+        ctx.save_for_backward(pos, ei, off)
+        ctx.coeff, ctx.cutoff = float(coeff), float(cutoff)
+        ctx.set_materialize_grads(False)
+        return d, rbf, cut
+
+    @staticmethod
+    def backward(ctx, g_d, g_rbf, g_cut):
+        if not ctx.needs_input_grad[0] or (g_d is None and g_rbf is None and g_cut is None):
+            return None, None, None, None, None
+        pos, ei, off = ctx.saved_tensors
+        g_vec = SchNetFeaturizeBwdFn.apply(pos, ei, off, ctx.coeff, ctx.cutoff, g_d, g_rbf, g_cut)
+        return EdgeVecToPosFn.apply(g_vec, ei, pos.shape[0]), None, None, None, None
+
+
+class SchNetFeaturizeBwdFn(torch.autograd.Function):
+    """g_vec (E, 3) from pos and the cotangents g_d / g_rbf / g_cut (each may be None)
+    (gmp_schnet_featurize_bwd_f32); backward by gmp_schnet_featurize_bwd2_f32, whose h_vec goes
+    to pos through the segmented sums.  The second backward is once-differentiable."""
+
+    @staticmethod
+    def forward(ctx, pos, ei, off, coeff, cutoff, g_d, g_rbf, g_cut):
+        ctx.save_for_backward(pos, ei, off, g_d, g_rbf, g_cut)
+        ctx.coeff, ctx.cutoff = coeff, cutoff
+        opt = [_f32c(t) if t is not None else None for t in (g_d, g_rbf, g_cut)]
+        return _lib.torch_ops().schnet_featurize_bwd(_f32c(pos), ei, off, coeff, cutoff, *opt)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, a_vec):
+        pos, ei, off, *opt = ctx.saved_tensors
+        g_d, g_rbf, g_cut = [_f32c(t) if t is not None else None for t in opt]
+        need = ctx.needs_input_grad
+        want = (g_d is not None and need[5], g_rbf is not None and need[6],
+                g_cut is not None and need[7], need[0])
+        gg_d, gg_rbf, gg_cut, h_vec = _lib.torch_ops().schnet_featurize_bwd2(
+            _f32c(pos), ei, off, ctx.coeff, ctx.cutoff, g_d, g_rbf, g_cut, _f32c(a_vec), *want)
+        dpos = edge_vec_to_pos_grad(h_vec, ei, pos.shape[0]) if want[3] else None
+        return (dpos, None, None, None, None, gg_d if want[0] else None,
+                gg_rbf if want[1] else None, gg_cut if want[2] else None)
+
+
+class SegmentReduce2Fn(torch.autograd.Function):
+    """SegmentReduceFn for sum / mean whose backward is recorded: the gather of g (scaled by
+    1 / count for the mean) is SegmentGatherFn, and each is the other's transpose."""
+
+    @staticmethod
+    def forward(ctx, src2d, csr, reduce):
+        ctx.csr, ctx.reduce, ctx.n = csr, reduce, src2d.shape[0]
+        return segment_reduce(src2d, csr, reduce)[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        return SegmentGatherFn.apply(g, ctx.csr, ctx.reduce, ctx.n), None, None
+
+
+class SegmentGatherFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, g, csr, reduce, n_items):
+        ctx.csr, ctx.reduce = csr, reduce
+        return segment_reduce_bwd(g.contiguous(), csr, reduce, None, n_items)
+
+    @staticmethod
+    def backward(ctx, a):
+        return SegmentReduce2Fn.apply(a, ctx.csr, ctx.reduce), None, None, None
+
+
+def segment_reduce_fn(src2d, csr, reduce):
+    """The segmented reduce as an autograd Function: twice differentiable for sum / mean inside
+    second_order(); max stays once-differentiable."""
+    if _SECOND_ORDER[0] and reduce in ("sum", "mean"):
+        return SegmentReduce2Fn.apply(src2d, csr, reduce)
+    return SegmentReduceFn.apply(src2d, csr, reduce)
+
+
+class GatherRows2Fn(torch.autograd.Function):
+    """GatherRowsFn whose backward (the segmented sum over the CSR of index) is recorded."""
+
+    @staticmethod
+    def forward(ctx, src2d, index, n_rows):
+        ctx.index, ctx.n_rows = index, n_rows
+        return gather_rows(src2d, index)
+
+    @staticmethod
+    def backward(ctx, g):
+        return SegmentReduce2Fn.apply(g, get_csr(ctx.index, ctx.n_rows), "sum"), None, None
+
+
+class EdgeLinear2Fn(torch.autograd.Function):
+    """EdgeLinearFn whose backward travels through autograd: dx = g W (EdgeDxFn) and (dW, db) =
+    (g^T x, colsum g) (EdgeOuterFn) are recorded, with no side stream and no deferred
+    accumulation."""
+
+    @staticmethod
+    def forward(ctx, x, W, b):
+        ctx.save_for_backward(x, W, b)
+        return torch.addmm(b, x, W.t()) if b is not None else x.mm(W.t())
+
+    @staticmethod
+    def backward(ctx, g):
+        x, W, b = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dx = EdgeDxFn.apply(g, W) if need[0] else None
+        need_w = need[1] and not _leaf_grad_unused(W)
+        need_b = b is not None and need[2] and not _leaf_grad_unused(b)
+        dW = db = None
+        if need_w or need_b:
+            dW, db = EdgeOuterFn.apply(g, x)
+        return dx, (dW if need_w else None), (db if need_b else None)
+
+
+class EdgeDxFn(torch.autograd.Function):
+    """dx = g W for W (n_out, n_in); backward: dg = a W^T (row GEMM), dW = g^T a (K = rows: the
+    deterministic outer sum; the library GEMM inside the op where a shape has no tile bucket).
+    Two orders are enough for force training: this backward is once-differentiable."""
+
+    @staticmethod
+    def forward(ctx, g, W):
+        ctx.save_for_backward(g, W)
+        return _dx(g.contiguous(), W)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, a):
+        g, W = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dg = torch.nn.functional.linear(a, W) if need[0] else None
+        dW = edge_outer_sum_rect(g, a)[0] if need[1] and not _leaf_grad_unused(W) else None
+        return dg, dW
+
+
+class EdgeOuterFn(torch.autograd.Function):
+    """(dW, db) = (g^T x, colsum(g)) over the rows (deterministic outer sum); backward: two plain
+    row GEMMs, dg = x aW^T + ab, dx = g aW."""
+
+    @staticmethod
+    def forward(ctx, g, x):
+        ctx.save_for_backward(g, x)
+        return edge_outer_sum_rect(g, x)
+
+    @staticmethod
+    def backward(ctx, aW, ab):
+        g, x = ctx.saved_tensors
+        dg = dx = None
+        if ctx.needs_input_grad[0]:
+            dg = x.mm(aW.t()) if aW is not None else None
+            if ab is not None:
+                dg = ab.expand(g.shape[0], -1) if dg is None else dg + ab
+        if ctx.needs_input_grad[1] and aW is not None:
+            dx = g.mm(aW)
+        return dg, dx

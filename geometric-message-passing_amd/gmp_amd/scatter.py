@@ -54,9 +54,8 @@ def scatter(src, index, dim=-1, out=None, dim_size=None, reduce="sum"):
     csr = _csr(index, n, out is not None or dim_size is not None)
     red = "sum" if reduce == "add" else reduce
     if out is None:
-        return ops.SegmentReduceFn.apply(x2, csr, red).reshape((n,) + tuple(shp[1:])).movedim(0,
-                                                                                            dim)
-    o = ops.SegmentReduceFn.apply(x2, csr, "sum").reshape((n,) + tuple(shp[1:])).movedim(0, dim)
+        return ops.segment_reduce_fn(x2, csr, red).reshape((n,) + tuple(shp[1:])).movedim(0, dim)
+    o = ops.segment_reduce_fn(x2, csr, "sum").reshape((n,) + tuple(shp[1:])).movedim(0, dim)
     out.add_(o)
     if red == "mean":
         out.div_(_bcast(csr.counts().clamp(min=1).to(out.dtype), out, dim))

@@ -62,8 +62,10 @@ class CFConv(MessagePassing):
             C = edge_cut
         W = self._filter(edge_attr)
         x = self.lin1(x)
-        if (not (C.requires_grad and torch.is_grad_enabled()) and self.fused_supported(x, W)):
-            # K13 with the cutoff applied to W at load time: W * C is never materialised
+        if ((ops.second_order_enabled() or not (C.requires_grad and torch.is_grad_enabled()))
+                and self.fused_supported(x, W)):
+            # K13 with the cutoff applied to W at load time: W * C is never materialised (inside
+            # ops.second_order() also when C carries a gradient: dC is gmp_cfconv_cgrad_f32)
             x = ops.cfconv_propagate(edge_index, x, W, C)
         else:
             x = self.propagate(edge_index, x=x, W=W * C.view(-1, 1))
@@ -133,7 +135,8 @@ class SchNetModel(nn.Module):
         # edge_weight, Gaussians and the cosine cutoff from one pass over the edges (K1,
         # gmp_schnet_featurize_f32); the cutoff is computed once and shared by every CFConv
         ds = self.distance_expansion
-        edge_weight, edge_attr, C = ops.SchNetFeaturizeFn.apply(
+        feat = ops.SchNetFeaturize2Fn if ops.second_order_enabled() else ops.SchNetFeaturizeFn
+        edge_weight, edge_attr, C = feat.apply(
             batch.pos, batch.edge_index, ds.offset, ds.coeff, self.cutoff)
         if not all(isinstance(i.conv, CFConv) and i.conv.cutoff == self.cutoff
                    for i in self.interactions):

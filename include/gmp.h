@@ -359,6 +359,20 @@ int gmp_schnet_featurize_bwd_f32(const float* pos, const int64_t* edge_index, in
                                  int num_gaussians, const float* offsets, float coeff,
                                  float cutoff, const float* g_dist, const float* g_rbf,
                                  const float* g_cut, float* g_vec, void* stream);
+/* Second order (energy-and-force training): the backward above, g_vec = s(dist) u with u = vec /
+ * dist and s = g_dist + sum_k g_rbf[k] rbf'_k + g_cut cut', differentiated once more.  a_vec (E,3)
+ * is the cotangent of g_vec and p = a_vec . u:
+ *   gg_dist (E) = p, gg_rbf (E,G) = rbf'_k p, gg_cut (E) = cut' p  (cotangents of g_dist / g_rbf /
+ *   g_cut), h_vec (E,3) = s' p u + (s / dist)(a_vec - p u)  (cotangent of vec; the caller
+ *   scatters it to pos as g_vec above).
+ * g_dist / g_rbf / g_cut and every output may be NULL.  Zero-length edges, and edges with an
+ * endpoint outside [0, n_nodes) (never read), give zeros in every output. */
+int gmp_schnet_featurize_bwd2_f32(const float* pos, int64_t n_nodes, const int64_t* edge_index,
+                                  int64_t n_edges, int num_gaussians, const float* offsets,
+                                  float coeff, float cutoff, const float* g_dist,
+                                  const float* g_rbf, const float* g_cut, const float* a_vec,
+                                  float* gg_dist, float* gg_rbf, float* gg_cut, float* h_vec,
+                                  void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * K16 irreps epilogues of the TP convolution (models/layers/tfn_layer.py:89-92), row-major
@@ -831,6 +845,15 @@ int gmp_cfconv_wgrad_scaled_f32(const float* g, int64_t n_g, const int64_t* gidx
                                 int64_t n_x, const int64_t* xidx, const float* escale,
                                 int64_t n_items, int64_t F, float* dw, int32_t* err,
                                 void* stream);
+/* The gradient w.r.t. the per-edge factor (and the fourth partial derivative of the multilinear
+ * form sum_e C[e] sum_f g[dst_e, f] x[src_e, f] W[e, f], from which every second-order term of
+ * CFConv follows by substitution):
+ *   dc[e] = (sum_f g[gidx[e], f] * x[xidx[e], f] * w[e, f]) (* escale[e])
+ * F % 4 == 0, g / x / w 16-byte aligned, escale may be NULL.  A fixed lane group per edge
+ * reduces in a fixed order (deterministic, no atomics); out-of-range -> dc[e] = 0, *err = 1. */
+int gmp_cfconv_cgrad_f32(const float* g, int64_t n_g, const int64_t* gidx, const float* x,
+                         int64_t n_x, const int64_t* xidx, const float* w, const float* escale,
+                         int64_t n_items, int64_t F, float* dc, int32_t* err, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * K14 shifted softplus (PyG ShiftedSoftplus, the SchNet filter-network / interaction
@@ -842,6 +865,11 @@ int gmp_cfconv_wgrad_scaled_f32(const float* g, int64_t n_g, const int64_t* gidx
 int gmp_ssp_fwd_f32(const float* x, int64_t n, float shift, float* y, void* stream);
 int gmp_ssp_bwd_f32(const float* x, const float* grad_y, int64_t n, float* grad_x,
                     void* stream);
+/* Second order: with a the cotangent of grad_x = grad_y sigmoid(x),
+ *   gg = a sigmoid(x) (cotangent of grad_y), gx = a grad_y sigmoid(x) (1 - sigmoid(x))
+ * (cotangent of x), in one pass; finite for every finite x (the product underflows to 0). */
+int gmp_ssp_bwd2_f32(const float* x, const float* grad_y, const float* a, int64_t n, float* gg,
+                     float* gx, void* stream);
 
 #ifdef __cplusplus
 }
