@@ -32,7 +32,10 @@ namespace {
 // SAVE (training): also write the LayerNorm outputs x_hat1, x_hat2 (and x_hat3 when save_planes
 // is 3) into xsave ((save_planes, E, d), rows in receiver-sorted edge order) and their 1/std
 // (rsave, (E, 3)) for the backward.
-template <int D, int ACT, bool MSG_MEAN, bool SAVE, bool HF>
+// POSB = false: the message branch alone (nobody reads this layer's position output): no W3
+// image, product, LN3 or w4 dot, no pos_aggr scan or store (pos_aggr may be null), column 2 of
+// rsave left unwritten; m_aggr, x_hat1, x_hat2 and rsave[:, 0:2] are bitwise the full kernel's.
+template <int D, int ACT, bool MSG_MEAN, bool SAVE, bool HF, bool POSB>
 __global__ __launch_bounds__(fwd_waves<HF>() * 64, fwd_waves<HF>() / 4) void egnn_fwd_kernel(
     int64_t n_nodes, int64_t n_edges, const float* __restrict__ AB, const float* __restrict__ pos,
     const int64_t* __restrict__ rowptr, const int64_t* __restrict__ recv,
@@ -49,11 +52,13 @@ __global__ __launch_bounds__(fwd_waves<HF>() * 64, fwd_waves<HF>() / 4) void egn
   float* sVw = smem + smem_vec_off<D, fwd_waves<HF>(), HF>();
   const float* sV = sVw;
   float* carry0 = smem + smem_carry_off<D, fwd_waves<HF>(), HF>();
-  if constexpr (HF) load_params_hf<D, false, 3, ACT>(sVw, hW, carry0, P);
-  else load_params_to_lds<D>(smem, P);
+  constexpr int NMAT = POSB ? 2 : 1;
+  if constexpr (HF) load_params_hf<D, false, POSB ? 3 : 1, ACT, NMAT>(sVw, hW, carry0, P);
+  else load_params_to_lds<D, false, NMAT>(smem, P);
   __syncthreads();
   const int sw2 = HF ? (int)sV[NV * D] : 0, sw3 = HF ? (int)sV[NV * D + 1] : 0;
   const int ex2 = HF ? (int)sV[NV * D + 2] : 0, ex3 = HF ? (int)sV[NV * D + 3] : 0;
+  (void)sW3; (void)hW3; (void)sw3; (void)ex3;
   constexpr bool XS = ACT == GMP_ACT_RELU;  // relu: y1 comes pre-scaled for the W2 product
 
   const int lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4;
@@ -61,8 +66,8 @@ __global__ __launch_bounds__(fwd_waves<HF>() * 64, fwd_waves<HF>() / 4) void egn
   float* cbuf = carry0 + (wid * 4 + g) * carry_stride<D>();
   carry_clear<D>(carry0 + wid * 4 * carry_stride<D>(), lane);
   const WaveRange wr = wave_range(rowptr, n_nodes, n_edges, n_waves, wid, fwd_waves<HF>());
-  zero_isolated<D>(wr, rowptr, m_aggr, pos_aggr, lane);
-  const float b4 = P.b4[0];
+  zero_isolated<D, POSB>(wr, rowptr, m_aggr, pos_aggr, lane);
+  const float b4 = POSB ? P.b4[0] : 0.f;
   int carry_node = -1;
   EdgeIJ nxt = load_ij(wr.e_lo, li, wr.e_hi, recv, send);
   // land the first ids before the loop, so that the wait at the loop head only has to cover
@@ -102,39 +107,45 @@ __global__ __launch_bounds__(fwd_waves<HF>() * 64, fwd_waves<HF>() / 4) void egn
     affine_act<D, ACT>(m, sV, V_LN2W, V_LN2B, g);  // (unscaled: m is also the message)
 
     // y3 = act(LN3(W3 m + b3)); s = w4 . y3 + b4   (x reused)
-    float r3;
-    if constexpr (HF) {
-      load_vec<D>(x, sV, V_B3S, g);
-      gemm_h2s<D, false>(hW3, ex3, m, x, li, g);
-      r3 = ln_rms<D>(x, eps, ex3 + sw3);
-    } else {
-      load_vec<D>(x, sV, V_B3, g);
-      gemm_wx<D>(sW3, m, x, li, g);
-      r3 = ln_normalize<D, false>(x, eps);
-    }
-    if (SAVE) {
-      if (save_planes == 3)
-        store_row_w<D, kAuxNT>(rows_window(xsave + 2 * ED, base, ne, D), eoff, x, g);
-      store3_w<kAuxNT>(rows_window(rsave, base, ne, 3), (g == 0 && c.valid) ? li * 12u : kOob,
-                       r1, r2, r3);
-    }
-    affine_act<D, ACT>(x, sV, V_LN3W, V_LN3B, g);
-    float sp = 0.f;
+    float s_e = 0.f;
+    if constexpr (POSB) {
+      float r3;
+      if constexpr (HF) {
+        load_vec<D>(x, sV, V_B3S, g);
+        gemm_h2s<D, false>(hW3, ex3, m, x, li, g);
+        r3 = ln_rms<D>(x, eps, ex3 + sw3);
+      } else {
+        load_vec<D>(x, sV, V_B3, g);
+        gemm_wx<D>(sW3, m, x, li, g);
+        r3 = ln_normalize<D, false>(x, eps);
+      }
+      if (SAVE) {
+        if (save_planes == 3)
+          store_row_w<D, kAuxNT>(rows_window(xsave + 2 * ED, base, ne, D), eoff, x, g);
+        store3_w<kAuxNT>(rows_window(rsave, base, ne, 3), (g == 0 && c.valid) ? li * 12u : kOob,
+                         r1, r2, r3);
+      }
+      affine_act<D, ACT>(x, sV, V_LN3W, V_LN3B, g);
+      float sp = 0.f;
 #pragma unroll
-    for (int p = 0; p < T; ++p) {
-      const f32x4 w = vec4<D>(sV, V_W4, p, g);
-      sp += w[0] * x[p][0] + w[1] * x[p][1] + w[2] * x[p][2] + w[3] * x[p][3];
+      for (int p = 0; p < T; ++p) {
+        const f32x4 w = vec4<D>(sV, V_W4, p, g);
+        sp += w[0] * x[p][0] + w[1] * x[p][1] + w[2] * x[p][2] + w[3] * x[p][3];
+      }
+      s_e = sum_groups(sp) + b4;
+    } else if (SAVE) {
+      store2_w<kAuxNT>(rows_window(rsave, base, ne, 3), (g == 0 && c.valid) ? li * 12u : kOob, r1,
+                       r2);
     }
-    const float s_e = sum_groups(sp) + b4;
 
     // segmented sums over receivers: m -> m_aggr (sum / mean), rel*s -> pos_aggr (mean)
     const int head = c.valid ? (int)((c.seg0 > base) ? (c.seg0 - base) : 0) : li;
     const bool is_end = c.valid && (c.e == c.seg1 - 1);
     const bool take = (li == 0) && c.valid && (c.i == carry_node);
     float pv[3] = {c.rx * s_e, c.ry * s_e, c.rz * s_e};
-    carry_apply<D>(cbuf, m, pv, take);
+    carry_apply<D, POSB>(cbuf, m, pv, take);
     seg_scan<T>(m, li, head);
-    {
+    if constexpr (POSB) {
       f32x4 pw[1] = {{pv[0], pv[1], pv[2], 0.f}};
       seg_scan<1>(pw, li, head);
       pv[0] = pw[0][0]; pv[1] = pw[0][1]; pv[2] = pw[0][2];
@@ -151,12 +162,13 @@ __global__ __launch_bounds__(fwd_waves<HF>() * 64, fwd_waves<HF>() / 4) void egn
       const int nn = max(i1 - i0 + 1, 0);  // (receiver-sorted: i0 <= i <= i1)
       store_row_w<D, 0>(rows_window(m_aggr, i0, nn, D), is_end ? (unsigned)((c.i - i0) * D * 4) : kOob,
                         m, g);
-      store3_w<0>(rows_window(pos_aggr, i0, nn, 3),
-                  (is_end && g == 0) ? (unsigned)((c.i - i0) * 12) : kOob,
-                  HF ? pv[0] * rdeg : pv[0] / deg, HF ? pv[1] * rdeg : pv[1] / deg,
-                  HF ? pv[2] * rdeg : pv[2] / deg);
+      if constexpr (POSB)
+        store3_w<0>(rows_window(pos_aggr, i0, nn, 3),
+                    (is_end && g == 0) ? (unsigned)((c.i - i0) * 12) : kOob,
+                    HF ? pv[0] * rdeg : pv[0] / deg, HF ? pv[1] * rdeg : pv[1] / deg,
+                    HF ? pv[2] * rdeg : pv[2] / deg);
     }
-    if (li == 15) carry_store<D>(cbuf, m, pv);
+    if (li == 15) carry_store<D, POSB>(cbuf, m, pv);
     carry_node = __builtin_amdgcn_readlane(c.i, 15);
   }
 }
@@ -197,7 +209,14 @@ __device__ __forceinline__ float vslot(const float* sV, int v, int s, int g) {
 //   0: nothing (the forward saved x_hat1..3: save_planes 3);
 //   1: x_hat3 from x_hat2 (the forward saved x_hat1, x_hat2: save_planes 2, the default).
 // (r03 also measured rebuilding x_hat1 / x_hat2 from the node projections AB: slower, removed.)
-template <int D, int ACT, bool MSG_MEAN, bool HF, bool AMAX, int RC>
+// POSB = false: for g_pos_aggr == 0 everywhere (nobody used the layer's position output; g_paggr,
+// dpre3_out may be null, x_hat3 / rsave[:, 2] are not read): no x_hat3 rebuild, LN3 backward,
+// dpre3 store or W3^T product and no W3^T image; dm = g_m_aggr[i] gscale, gdiff = rinv r; the
+// ln3w / ln3b / w4 / b4 partial slots are zeros and amax[1] is left alone.  Every other output
+// is bitwise the full kernel's at g_pos_aggr = 0.
+// GPOS = false: the caller wants no position gradient (dpos_recv, gdiff_out may be null): no
+// s_e / dd / gdiff, no gdiff scan or store; every other output unchanged.
+template <int D, int ACT, bool MSG_MEAN, bool HF, bool AMAX, int RC, bool POSB, bool GPOS>
 __global__ __launch_bounds__(kBwdWaves * 64, 2) void egnn_bwd_kernel(
     int64_t n_nodes, int64_t n_edges, const float* __restrict__ pos,
     const int64_t* __restrict__ rowptr, const int64_t* __restrict__ recv,
@@ -218,11 +237,14 @@ __global__ __launch_bounds__(kBwdWaves * 64, 2) void egnn_bwd_kernel(
   const float* sV = sVw;
   // (HF: W3^T centred as the forward's W3, so the x_hat3 recompute is bitwise the forward's; W2 as
   // given)
-  if constexpr (HF) load_params_hf<D, true, 2, ACT>(sVw, hW, smem + smem_carry_off<D, kBwdWaves, HF>(), P);
-  else load_params_to_lds<D, true>(smem, P);
+  constexpr int NMAT = POSB ? 2 : 1;
+  if constexpr (HF)
+    load_params_hf<D, true, POSB ? 2 : 0, ACT, NMAT>(sVw, hW, smem + smem_carry_off<D, kBwdWaves, HF>(), P);
+  else load_params_to_lds<D, true, NMAT>(smem, P);
   __syncthreads();
   const int sw2 = HF ? (int)sV[NV * D] : 0, sw3 = HF ? (int)sV[NV * D + 1] : 0;
   const int ex3 = HF ? (int)sV[NV * D + 3] : 0;  // the forward's static W3 input exponent
+  (void)sW3t; (void)hW3t; (void)sw3; (void)ex3;
   const float* xr1 = xsave;
   const float* xr2 = xsave + (size_t)n_edges * D;
   // AMAX: per-chunk wave maxima go to two LDS words (no loop-carried registers: the kernel sits
@@ -238,8 +260,8 @@ __global__ __launch_bounds__(kBwdWaves * 64, 2) void egnn_bwd_kernel(
   float* cbuf = smem + smem_carry_off<D, kBwdWaves, HF>() + (wid * 4 + g) * carry_stride<D>();
   carry_clear<D>(smem + smem_carry_off<D, kBwdWaves, HF>() + wid * 4 * carry_stride<D>(), lane);
   const WaveRange wr = wave_range(rowptr, n_nodes, n_edges, n_waves, wid, kBwdWaves);
-  zero_isolated<D>(wr, rowptr, dA, dpos_recv, lane);
-  const float b4 = P.b4[0];
+  zero_isolated<D, GPOS>(wr, rowptr, dA, dpos_recv, lane);
+  const float b4 = POSB ? P.b4[0] : 0.f;
   const size_t ED = (size_t)n_edges * D;
 
   float vacc[NVG][K];
@@ -263,17 +285,22 @@ __global__ __launch_bounds__(kBwdWaves * 64, 2) void egnn_bwd_kernel(
     // round trip); lanes past the range are zeroed through ds / gscale / rstd = 0
     const float rs1 = rsave[3 * (size_t)c.ec + 0];
     const float rs2 = rsave[3 * (size_t)c.ec + 1];
-    const float rs3 = rsave[3 * (size_t)c.ec + 2];
-    const float gp0 = g_paggr[3 * c.i + 0], gp1 = g_paggr[3 * c.i + 1], gp2 = g_paggr[3 * c.i + 2];
+    float rs3 = 0.f, gp0 = 0.f, gp1 = 0.f, gp2 = 0.f;
     f32x4 x[T], xh2[T], z[T];
-    if constexpr (RC == 1) load_row<D>(x, rowp(xsave + ED, c.ec, D), g);  // x = xhat2
-    else load_row<D>(z, rowp(xsave + 2 * ED, c.ec, D), g);               // z = xhat3
+    if constexpr (POSB) {
+      rs3 = rsave[3 * (size_t)c.ec + 2];
+      gp0 = g_paggr[3 * c.i + 0], gp1 = g_paggr[3 * c.i + 1], gp2 = g_paggr[3 * c.i + 2];
+      if constexpr (RC == 1) load_row<D>(x, rowp(xsave + ED, c.ec, D), g);  // x = xhat2
+      else load_row<D>(z, rowp(xsave + 2 * ED, c.ec, D), g);               // z = xhat3
+    } else {
+      load_row<D>(xh2, rowp(g_maggr, c.i, D), g);  // g_m_aggr[i] (dm, below)
+    }
     __builtin_amdgcn_sched_barrier(0);
-    edge_geom<HF>(c);
+    edge_geom<HF, true>(c);
     const float rstd1 = c.valid ? rs1 : 0.f;
     const float rstd2 = c.valid ? rs2 : 0.f;
     const float rstd3 = c.valid ? rs3 : 0.f;
-    if constexpr (RC == 1) {
+    if constexpr (POSB && RC == 1) {
       // z = xhat3 = LN3(W3 act(LN2 affine(xhat2)) + b3) with the forward's 1/std: the forward's
       // products (same operands, planes, scales and MFMA order) -> bitwise its x_hat3
       if constexpr (HF) {
@@ -297,45 +324,58 @@ __global__ __launch_bounds__(kBwdWaves * 64, 2) void egnn_bwd_kernel(
     const float gpx = gp0 * inv_deg;
     const float gpy = gp1 * inv_deg;
     const float gpz = gp2 * inv_deg;
-    const float ds = gpx * c.rx + gpy * c.ry + gpz * c.rz;  // dL/ds_e
-    if (g == 0) db4 += ds;
+    // chunk windows: edges [base, base + ne) of the per-edge tensors, receivers [i0, i1]
+    auto chunk_window = [&](int& ne, int& i0, int& i1, unsigned& eoff) {
+      ne = __builtin_amdgcn_readfirstlane(min(16, wr.e_hi - base));
+      i0 = __builtin_amdgcn_readfirstlane(c.i);
+      i1 = __builtin_amdgcn_readlane(c.i, 15);
+      eoff = c.valid ? (unsigned)(li * D * 4) : kOob;
+    };
+    int ne, i0, i1;
+    unsigned eoff;
+    float s_e = 0.f;
+    if constexpr (!POSB) {
+      chunk_window(ne, i0, i1, eoff);
+    } else {
+      const float ds = gpx * c.rx + gpy * c.ry + gpz * c.rz;  // dL/ds_e
+      if (g == 0) db4 += ds;
 
-    float sp = 0.f;
+      float sp = 0.f;
 #pragma unroll
-    for (int p = 0; p < T; ++p) {
-      const f32x4 w3 = vec4<D>(sV, V_LN3W, p, g), b3 = vec4<D>(sV, V_LN3B, p, g);
-      const f32x4 w4 = vec4<D>(sV, V_W4, p, g);
+      for (int p = 0; p < T; ++p) {
+        const f32x4 w3 = vec4<D>(sV, V_LN3W, p, g), b3 = vec4<D>(sV, V_LN3B, p, g);
+        const f32x4 w4 = vec4<D>(sV, V_W4, p, g);
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float zz = z[p][q] * w3[q] + b3[q];
-        sp += w4[q] * act_f<ACT>(zz);
-        x[p][q] = ds * w4[q] * act_df<ACT>(zz);  // dz3 (m already stored)
+        for (int q = 0; q < 4; ++q) {
+          const float zz = z[p][q] * w3[q] + b3[q];
+          sp += w4[q] * act_f<ACT>(zz);
+          x[p][q] = ds * w4[q] * act_df<ACT>(zz);  // dz3 (m already stored)
+        }
       }
-    }
-    const float s_e = sum_groups(sp) + b4;
-    accumulate_vec<D>([&](int s) {
-      return ds * act_f<ACT>(slot<D>(z, s) * vslot<D>(sV, V_LN3W, s, g) + vslot<D>(sV, V_LN3B, s, g));
-    }, vacc[G_W4], li);
-    accumulate_vec<D>([&](int s) { return slot<D>(x, s) * slot<D>(z, s); }, vacc[G_LN3W], li);
-    accumulate_vec<D>([&](int s) { return slot<D>(x, s); }, vacc[G_LN3B], li);
-    load_row<D>(xh2, rowp(g_maggr, c.i, D), g);  // g_m_aggr[i] (dm seed, below)
-    __builtin_amdgcn_sched_barrier(0);             // issue it here, ahead of the LN backward
+      s_e = sum_groups(sp) + b4;
+      accumulate_vec<D>([&](int s) {
+        return ds * act_f<ACT>(slot<D>(z, s) * vslot<D>(sV, V_LN3W, s, g) + vslot<D>(sV, V_LN3B, s, g));
+      }, vacc[G_W4], li);
+      accumulate_vec<D>([&](int s) { return slot<D>(x, s) * slot<D>(z, s); }, vacc[G_LN3W], li);
+      accumulate_vec<D>([&](int s) { return slot<D>(x, s); }, vacc[G_LN3B], li);
+      load_row<D>(xh2, rowp(g_maggr, c.i, D), g);  // g_m_aggr[i] (dm seed, below)
+      __builtin_amdgcn_sched_barrier(0);             // issue it here, ahead of the LN backward
 #pragma unroll
-    for (int p = 0; p < T; ++p) x[p] *= vec4<D>(sV, V_LN3W, p, g);
-    ln_backward<D>(x, z, rstd3);  // x = dpre3
-    if (AMAX) fold_max<D>(lmx + 1, x, lane);
-    const int ne = __builtin_amdgcn_readfirstlane(min(16, wr.e_hi - base));
-    const int i0 = __builtin_amdgcn_readfirstlane(c.i);
-    const int i1 = __builtin_amdgcn_readlane(c.i, 15);
-    const unsigned eoff = c.valid ? (unsigned)(li * D * 4) : kOob;
-    store_row_w<D, kAuxNT>(rows_window(dpre3_out, base, ne, D), eoff, x, g);
+      for (int p = 0; p < T; ++p) x[p] *= vec4<D>(sV, V_LN3W, p, g);
+      ln_backward<D>(x, z, rstd3);  // x = dpre3
+      if (AMAX) fold_max<D>(lmx + 1, x, lane);
+      chunk_window(ne, i0, i1, eoff);
+      store_row_w<D, kAuxNT>(rows_window(dpre3_out, base, ne, D), eoff, x, g);
+    }
 
     // ---------------- dm = g_m_aggr[i] (/deg) + W3^T dpre3   (z); xhat2 -> xh2 in flight
 #pragma unroll
     for (int p = 0; p < T; ++p) z[p] = xh2[p] * gscale;
     load_row<D>(xh2, rowp(xr2, c.ec, D), g);
-    if constexpr (HF) gemm_h2<D, true>(hW3t, sw3, 0, x, z, li, g);  // z += W3^T dpre3
-    else gemm_wx<D, 2>(sW3t, x, z, li, g);
+    if constexpr (POSB) {
+      if constexpr (HF) gemm_h2<D, true>(hW3t, sw3, 0, x, z, li, g);  // z += W3^T dpre3
+      else gemm_wx<D, 2>(sW3t, x, z, li, g);
+    }
 #pragma unroll
     for (int p = 0; p < T; ++p) {
       const f32x4 w = vec4<D>(sV, V_LN2W, p, g), b = vec4<D>(sV, V_LN2B, p, g);
@@ -370,28 +410,41 @@ __global__ __launch_bounds__(kBwdWaves * 64, 2) void egnn_bwd_kernel(
     store_row_w<D, kAuxNT>(rows_window(dpre1_out, base, ne, D), eoff, x, g);
 
     // dw1d += dpre1 * dist ; d(dist) = w1d . dpre1
-    float dd = 0.f;
-#pragma unroll
-    for (int p = 0; p < T; ++p) {
-      const f32x4 w = vec4<D>(sV, V_W1D, p, g);
-      dd += w[0] * x[p][0] + w[1] * x[p][1] + w[2] * x[p][2] + w[3] * x[p][3];
-    }
-    dd = sum_groups(dd);
     const float dist = c.dist;
-    accumulate_vec<D>([&](int s) { return slot<D>(x, s) * dist; }, vacc[G_W1D], li);
+    float gd[3] = {0.f, 0.f, 0.f};
+    if constexpr (GPOS) {
+      float dd = 0.f;
+#pragma unroll
+      for (int p = 0; p < T; ++p) {
+        const f32x4 w = vec4<D>(sV, V_W1D, p, g);
+        dd += w[0] * x[p][0] + w[1] * x[p][1] + w[2] * x[p][2] + w[3] * x[p][3];
+      }
+      dd = sum_groups(dd);
+      accumulate_vec<D>([&](int s) { return slot<D>(x, s) * dist; }, vacc[G_W1D], li);
 
-    const float rinv = (c.dist > 0.f) ? dd / c.dist : 0.f;
-    float gd[3] = {gpx * s_e + rinv * c.rx, gpy * s_e + rinv * c.ry, gpz * s_e + rinv * c.rz};
-    store3_w<kAuxNT>(rows_window(gdiff_out, base, ne, 3), (c.valid && g == 0) ? li * 12u : kOob,
-                     gd[0], gd[1], gd[2]);
+      const float rinv = (c.dist > 0.f) ? dd / c.dist : 0.f;
+      if constexpr (POSB) {
+        gd[0] = gpx * s_e + rinv * c.rx;
+        gd[1] = gpy * s_e + rinv * c.ry;
+        gd[2] = gpz * s_e + rinv * c.rz;
+      } else {
+        gd[0] = rinv * c.rx;
+        gd[1] = rinv * c.ry;
+        gd[2] = rinv * c.rz;
+      }
+      store3_w<kAuxNT>(rows_window(gdiff_out, base, ne, 3), (c.valid && g == 0) ? li * 12u : kOob,
+                       gd[0], gd[1], gd[2]);
+    } else {
+      accumulate_vec<D>([&](int s) { return slot<D>(x, s) * dist; }, vacc[G_W1D], li);
+    }
 
     // ---------------- receiver-side segmented sums: dA (dpre1), dpos_recv (gdiff)
     const int head = c.valid ? (int)((c.seg0 > base) ? (c.seg0 - base) : 0) : li;
     const bool is_end = c.valid && (c.e == c.seg1 - 1);
     const bool take = (li == 0) && c.valid && (c.i == carry_node);
-    carry_apply<D>(cbuf, x, gd, take);
+    carry_apply<D, GPOS>(cbuf, x, gd, take);
     seg_scan<T>(x, li, head);
-    {
+    if constexpr (GPOS) {
       f32x4 pw[1] = {{gd[0], gd[1], gd[2], 0.f}};
       seg_scan<1>(pw, li, head);
       gd[0] = pw[0][0]; gd[1] = pw[0][1]; gd[2] = pw[0][2];
@@ -400,18 +453,20 @@ __global__ __launch_bounds__(kBwdWaves * 64, 2) void egnn_bwd_kernel(
       const int nn = max(i1 - i0 + 1, 0);  // (receiver-sorted: i0 <= i <= i1)
       store_row_w<D, 0>(rows_window(dA, i0, nn, D), is_end ? (unsigned)((c.i - i0) * D * 4) : kOob,
                         x, g);
-      store3_w<0>(rows_window(dpos_recv, i0, nn, 3),
-                  (is_end && g == 0) ? (unsigned)((c.i - i0) * 12) : kOob, gd[0], gd[1], gd[2]);
+      if constexpr (GPOS)
+        store3_w<0>(rows_window(dpos_recv, i0, nn, 3),
+                    (is_end && g == 0) ? (unsigned)((c.i - i0) * 12) : kOob, gd[0], gd[1], gd[2]);
     }
-    if (li == 15) carry_store<D>(cbuf, x, gd);
+    if (li == 15) carry_store<D, GPOS>(cbuf, x, gd);
     carry_node = __builtin_amdgcn_readlane(c.i, 15);
   }
 
   // ---------------- workgroup reduction of the vector grads -> partials[blockIdx]
   __syncthreads();  // every wave is done with W2/W3: reuse that LDS as scratch
-  if (AMAX && threadIdx.x == 0) {  // (invalid lanes held zeros: gscale / rstd = 0)
+  // (the variants are built with AMAX alone and take a null amax here)
+  if (AMAX && threadIdx.x == 0 && ((POSB && GPOS) || amax)) {  // (invalid lanes held zeros: gscale / rstd = 0)
     atomicMax(&amax[0], lmx[0]);
-    atomicMax(&amax[1], lmx[1]);
+    if (POSB) atomicMax(&amax[1], lmx[1]);
   }
   __syncthreads();
   float* red = smem;  // [wave][NVG*D + 1]
@@ -444,7 +499,7 @@ int64_t n_waves_for(int64_t n_edges, int nwb) {
   return ceil_div(w, nwb) * nwb;
 }
 
-template <int D, int ACT, bool MEAN>
+template <int D, int ACT, bool MEAN, bool POSB>
 int launch_fwd(int64_t N, int64_t E, const float* AB, const float* pos, const int64_t* rowptr,
                const int64_t* recv, const int64_t* send, const gmp_egnn_params& P, float eps,
                float* m_aggr, float* pos_aggr, float* xsave, int save_planes, float* rsave,
@@ -452,12 +507,13 @@ int launch_fwd(int64_t N, int64_t E, const float* AB, const float* pos, const in
   const bool hf = !egnn_f32();
   const int nwb = hf ? fwd_waves<true>() : fwd_waves<false>();
   const int64_t W = n_waves_for(E, nwb);
-  const size_t smem = hf ? smem_total<D, fwd_waves<true>(), true>()
-                         : smem_total<D, fwd_waves<false>(), false>();
-  auto k = rsave ? (hf ? egnn_fwd_kernel<D, ACT, MEAN, true, true>
-                       : egnn_fwd_kernel<D, ACT, MEAN, true, false>)
-                 : (hf ? egnn_fwd_kernel<D, ACT, MEAN, false, true>
-                       : egnn_fwd_kernel<D, ACT, MEAN, false, false>);
+  constexpr int NMAT = POSB ? 2 : 1;
+  const size_t smem = hf ? smem_total<D, fwd_waves<true>(), true, NMAT>()
+                         : smem_total<D, fwd_waves<false>(), false, NMAT>();
+  auto k = rsave ? (hf ? egnn_fwd_kernel<D, ACT, MEAN, true, true, POSB>
+                       : egnn_fwd_kernel<D, ACT, MEAN, true, false, POSB>)
+                 : (hf ? egnn_fwd_kernel<D, ACT, MEAN, false, true, POSB>
+                       : egnn_fwd_kernel<D, ACT, MEAN, false, false, POSB>);
   int rc = prep_kernel(k, smem);
   if (rc) return rc;
   k<<<(unsigned)(W / nwb), nwb * 64, smem, s>>>(N, E, AB, pos, rowptr, recv, send, P,
@@ -466,7 +522,9 @@ int launch_fwd(int64_t N, int64_t E, const float* AB, const float* pos, const in
   return launch_status();
 }
 
-template <int D, int ACT, bool MEAN>
+// The full kernel in its four (AMAX, RC) forms; the variants with AMAX alone (a null amax is
+// checked in the kernel) and, without the position branch, in one RC form (x_hat3 is not read).
+template <int D, int ACT, bool MEAN, bool POSB, bool GPOS>
 int launch_bwd(int64_t N, int64_t E, const float* pos, const int64_t* rowptr,
                const int64_t* recv, const int64_t* send, const gmp_egnn_params& P,
                const float* xsave, int save_planes, const float* rsave, const float* gm,
@@ -474,13 +532,18 @@ int launch_bwd(int64_t N, int64_t E, const float* pos, const int64_t* rowptr,
                float* dpre2, float* dpre3, float* partials, unsigned* amax, hipStream_t s) {
   const int64_t W = n_waves_for(E, kBwdWaves);
   const bool hf = !egnn_f32();
-  const size_t smem = hf ? smem_total<D, kBwdWaves, true>() : smem_total<D, kBwdWaves, false>();
-#define LAUNCH_BWD_K(RC)                                                  \
-  (hf ? (amax ? egnn_bwd_kernel<D, ACT, MEAN, true, true, RC>          \
-              : egnn_bwd_kernel<D, ACT, MEAN, true, false, RC>)        \
-      : (amax ? egnn_bwd_kernel<D, ACT, MEAN, false, true, RC>         \
-              : egnn_bwd_kernel<D, ACT, MEAN, false, false, RC>))
-  auto k = save_planes == 3 ? LAUNCH_BWD_K(0) : LAUNCH_BWD_K(1);
+  constexpr int NMAT = POSB ? 2 : 1;
+  constexpr bool FULL = POSB && GPOS;
+  constexpr int RC0 = POSB ? 0 : 1;  // the save_planes == 3 form
+  const size_t smem = hf ? smem_total<D, kBwdWaves, true, NMAT>()
+                         : smem_total<D, kBwdWaves, false, NMAT>();
+  const bool ax = !FULL || amax;
+#define LAUNCH_BWD_K(RC)                                                              \
+  (hf ? (ax ? egnn_bwd_kernel<D, ACT, MEAN, true, true, RC, POSB, GPOS>              \
+            : egnn_bwd_kernel<D, ACT, MEAN, true, !FULL, RC, POSB, GPOS>)            \
+      : (ax ? egnn_bwd_kernel<D, ACT, MEAN, false, true, RC, POSB, GPOS>             \
+            : egnn_bwd_kernel<D, ACT, MEAN, false, !FULL, RC, POSB, GPOS>))
+  auto k = save_planes == 3 ? LAUNCH_BWD_K(RC0) : LAUNCH_BWD_K(1);
 #undef LAUNCH_BWD_K
   int rc = prep_kernel(k, smem);
   if (rc) return rc;
@@ -542,15 +605,18 @@ int gmp_egnn_set_f32_mfma(int on) {
   return prev;
 }
 
-int gmp_egnn_edge_fwd_f32(int64_t n_nodes, int64_t n_edges, int64_t d, const float* AB,
-                          const float* pos, const int64_t* rowptr, const int64_t* recv,
-                          const int64_t* send, const gmp_egnn_params* params, int act,
-                          int msg_mean, float ln_eps, float* m_aggr, float* pos_aggr,
-                          float* save_xhat, int save_planes, float* save_rstd, void* stream) {
+int gmp_egnn_edge_fwd_ex_f32(int64_t n_nodes, int64_t n_edges, int64_t d, const float* AB,
+                             const float* pos, const int64_t* rowptr, const int64_t* recv,
+                             const int64_t* send, const gmp_egnn_params* params, int act,
+                             int msg_mean, float ln_eps, float* m_aggr, float* pos_aggr,
+                             float* save_xhat, int save_planes, float* save_rstd, uint32_t flags,
+                             void* stream) {
   if (!(d == 32 || d == 64 || d == 128)) return GMP_ERR_UNSUPPORTED;
+  GMP_CHECK_ARG((flags & ~(uint32_t)GMP_EGNN_NO_POS_BRANCH) == 0);
+  const bool posb = !(flags & GMP_EGNN_NO_POS_BRANCH);
   GMP_CHECK_ARG(n_nodes >= 0 && n_edges >= 0 && (act == 0 || act == 1));
   GMP_CHECK_ARG(n_nodes < INT32_MAX && n_edges < INT32_MAX);  // 32-bit edge / node ids
-  GMP_CHECK_ARG(params_ok(params) && m_aggr && pos_aggr && rowptr);
+  GMP_CHECK_ARG(params_ok(params) && m_aggr && (pos_aggr || !posb) && rowptr);
   // training: save_rstd and save_xhat together, 2 (x_hat1, x_hat2) or 3 planes
   GMP_CHECK_ARG((save_rstd == nullptr) == (save_xhat == nullptr));
   GMP_CHECK_ARG(save_xhat == nullptr || save_planes == 2 || save_planes == 3);
@@ -559,23 +625,84 @@ int gmp_egnn_edge_fwd_f32(int64_t n_nodes, int64_t n_edges, int64_t d, const flo
   int rc = GMP_OK;
   if (n_edges == 0) {  // (otherwise the kernel writes every row: zero_isolated)
     rc = hip_check(hipMemsetAsync(m_aggr, 0, n_nodes * d * sizeof(float), s));
-    if (!rc) rc = hip_check(hipMemsetAsync(pos_aggr, 0, n_nodes * 3 * sizeof(float), s));
+    if (!rc && posb) rc = hip_check(hipMemsetAsync(pos_aggr, 0, n_nodes * 3 * sizeof(float), s));
     return rc;
   }
   GMP_CHECK_ARG(AB && pos && recv && send && aligned16(AB) && aligned16(m_aggr));
   GMP_CHECK_ARG(aligned16(params->W2) && aligned16(params->W3));
   GMP_CHECK_ARG(save_xhat == nullptr || aligned16(save_xhat));
 #define LAUNCH_CALL_FWD(DD, AA, MM)                                                              \
-  rc = launch_fwd<DD, AA, MM>(n_nodes, n_edges, AB, pos, rowptr, recv, send, *params, ln_eps, \
-                              m_aggr, pos_aggr, save_xhat, save_planes, save_rstd, s)
+  rc = posb ? launch_fwd<DD, AA, MM, true>(n_nodes, n_edges, AB, pos, rowptr, recv, send,      \
+                                           *params, ln_eps, m_aggr, pos_aggr, save_xhat,        \
+                                           save_planes, save_rstd, s)                           \
+            : launch_fwd<DD, AA, MM, false>(n_nodes, n_edges, AB, pos, rowptr, recv, send,     \
+                                            *params, ln_eps, m_aggr, pos_aggr, save_xhat,       \
+                                            save_planes, save_rstd, s)
   LAUNCH_EGNN_DISPATCH(LAUNCH_CALL_FWD);
 #undef LAUNCH_CALL_FWD
   return rc;
 }
 
+int gmp_egnn_edge_fwd_f32(int64_t n_nodes, int64_t n_edges, int64_t d, const float* AB,
+                          const float* pos, const int64_t* rowptr, const int64_t* recv,
+                          const int64_t* send, const gmp_egnn_params* params, int act,
+                          int msg_mean, float ln_eps, float* m_aggr, float* pos_aggr,
+                          float* save_xhat, int save_planes, float* save_rstd, void* stream) {
+  return gmp_egnn_edge_fwd_ex_f32(n_nodes, n_edges, d, AB, pos, rowptr, recv, send, params, act,
+                                  msg_mean, ln_eps, m_aggr, pos_aggr, save_xhat, save_planes,
+                                  save_rstd, 0u, stream);
+}
+
 int64_t gmp_egnn_edge_bwd_partials_rows(int64_t n_edges, int64_t d) {
   (void)d;
   return n_waves_for(n_edges, kBwdWaves) / kBwdWaves;
+}
+
+int gmp_egnn_edge_bwd_ex_f32(int64_t n_nodes, int64_t n_edges, int64_t d, const float* pos,
+                             const int64_t* rowptr, const int64_t* recv, const int64_t* send,
+                             const gmp_egnn_params* params, int act, int msg_mean,
+                             const float* save_xhat, int save_planes, const float* save_rstd,
+                             const float* g_m_aggr, const float* g_pos_aggr, float* dA,
+                             float* dpos_recv, float* dpre1, float* gdiff, float* dpre2,
+                             float* dpre3, float* vec_partials, uint32_t* amax, uint32_t flags,
+                             void* stream) {
+  if (!(d == 32 || d == 64 || d == 128)) return GMP_ERR_UNSUPPORTED;
+  GMP_CHECK_ARG((flags & ~(uint32_t)(GMP_EGNN_NO_POS_BRANCH | GMP_EGNN_NO_POS_GRAD)) == 0);
+  const bool posb = !(flags & GMP_EGNN_NO_POS_BRANCH), gpos = !(flags & GMP_EGNN_NO_POS_GRAD);
+  GMP_CHECK_ARG(n_nodes >= 0 && n_edges >= 0 && (act == 0 || act == 1));
+  GMP_CHECK_ARG(n_nodes < INT32_MAX && n_edges < INT32_MAX);  // 32-bit edge / node ids
+  GMP_CHECK_ARG(params_ok(params) && dA && (dpos_recv || !gpos) && rowptr && vec_partials);
+  GMP_CHECK_ARG(save_planes == 2 || save_planes == 3);
+  hipStream_t s = as_stream(stream);
+  int rc = GMP_OK;
+  if (n_nodes > 0 && n_edges == 0) {  // (otherwise the kernel writes every row: zero_isolated)
+    rc = hip_check(hipMemsetAsync(dA, 0, n_nodes * d * sizeof(float), s));
+    if (!rc && gpos) rc = hip_check(hipMemsetAsync(dpos_recv, 0, n_nodes * 3 * sizeof(float), s));
+  }
+  if (rc) return rc;
+  if (n_edges == 0 || n_nodes == 0) {
+    return hip_check(hipMemsetAsync(
+        vec_partials, 0,
+        gmp_egnn_edge_bwd_partials_rows(n_edges, d) * (8 * d + 1) * sizeof(float), s));
+  }
+  GMP_CHECK_ARG(pos && recv && send && save_xhat && save_rstd && g_m_aggr && dpre1 && dpre2);
+  GMP_CHECK_ARG(!posb || (g_pos_aggr && dpre3));
+  GMP_CHECK_ARG(!gpos || gdiff);
+  GMP_CHECK_ARG(aligned16(save_xhat) && aligned16(dA) && aligned16(g_m_aggr) &&
+                aligned16(dpre1) && aligned16(dpre2) && (!posb || aligned16(dpre3)));
+  GMP_CHECK_ARG(aligned16(params->W2) && aligned16(params->W3));
+#define LAUNCH_BWD_V(DD, AA, MM, PB, GP)                                                        \
+  launch_bwd<DD, AA, MM, PB, GP>(n_nodes, n_edges, pos, rowptr, recv, send, *params, save_xhat, \
+                                 save_planes, save_rstd, g_m_aggr, g_pos_aggr, dA, dpos_recv,   \
+                                 dpre1, gdiff, dpre2, dpre3, vec_partials, amax, s)
+#define LAUNCH_CALL_BWD(DD, AA, MM)                                                              \
+  rc = posb ? (gpos ? LAUNCH_BWD_V(DD, AA, MM, true, true) : LAUNCH_BWD_V(DD, AA, MM, true, false)) \
+            : (gpos ? LAUNCH_BWD_V(DD, AA, MM, false, true)                                     \
+                    : LAUNCH_BWD_V(DD, AA, MM, false, false))
+  LAUNCH_EGNN_DISPATCH(LAUNCH_CALL_BWD);
+#undef LAUNCH_CALL_BWD
+#undef LAUNCH_BWD_V
+  return rc;
 }
 
 int gmp_egnn_edge_bwd_amax_f32(int64_t n_nodes, int64_t n_edges, int64_t d, const float* pos,
@@ -585,35 +712,10 @@ int gmp_egnn_edge_bwd_amax_f32(int64_t n_nodes, int64_t n_edges, int64_t d, cons
                                const float* g_m_aggr, const float* g_pos_aggr, float* dA,
                                float* dpos_recv, float* dpre1, float* gdiff, float* dpre2,
                                float* dpre3, float* vec_partials, uint32_t* amax, void* stream) {
-  if (!(d == 32 || d == 64 || d == 128)) return GMP_ERR_UNSUPPORTED;
-  GMP_CHECK_ARG(n_nodes >= 0 && n_edges >= 0 && (act == 0 || act == 1));
-  GMP_CHECK_ARG(n_nodes < INT32_MAX && n_edges < INT32_MAX);  // 32-bit edge / node ids
-  GMP_CHECK_ARG(params_ok(params) && dA && dpos_recv && rowptr && vec_partials);
-  GMP_CHECK_ARG(save_planes == 2 || save_planes == 3);
-  hipStream_t s = as_stream(stream);
-  int rc = GMP_OK;
-  if (n_nodes > 0 && n_edges == 0) {  // (otherwise the kernel writes every row: zero_isolated)
-    rc = hip_check(hipMemsetAsync(dA, 0, n_nodes * d * sizeof(float), s));
-    if (!rc) rc = hip_check(hipMemsetAsync(dpos_recv, 0, n_nodes * 3 * sizeof(float), s));
-  }
-  if (rc) return rc;
-  if (n_edges == 0 || n_nodes == 0) {
-    return hip_check(hipMemsetAsync(
-        vec_partials, 0,
-        gmp_egnn_edge_bwd_partials_rows(n_edges, d) * (8 * d + 1) * sizeof(float), s));
-  }
-  GMP_CHECK_ARG(pos && recv && send && save_xhat && save_rstd && g_m_aggr && g_pos_aggr &&
-                dpre1 && gdiff && dpre2 && dpre3);
-  GMP_CHECK_ARG(aligned16(save_xhat) && aligned16(dA) && aligned16(g_m_aggr) &&
-                aligned16(dpre1) && aligned16(dpre2) && aligned16(dpre3));
-  GMP_CHECK_ARG(aligned16(params->W2) && aligned16(params->W3));
-#define LAUNCH_CALL_BWD(DD, AA, MM)                                                              \
-  rc = launch_bwd<DD, AA, MM>(n_nodes, n_edges, pos, rowptr, recv, send, *params, save_xhat,  \
-                              save_planes, save_rstd, g_m_aggr, g_pos_aggr, dA, dpos_recv,    \
-                              dpre1, gdiff, dpre2, dpre3, vec_partials, amax, s)
-  LAUNCH_EGNN_DISPATCH(LAUNCH_CALL_BWD);
-#undef LAUNCH_CALL_BWD
-  return rc;
+  return gmp_egnn_edge_bwd_ex_f32(n_nodes, n_edges, d, pos, rowptr, recv, send, params, act,
+                                  msg_mean, save_xhat, save_planes, save_rstd, g_m_aggr,
+                                  g_pos_aggr, dA, dpos_recv, dpre1, gdiff, dpre2, dpre3,
+                                  vec_partials, amax, 0u, stream);
 }
 
 int gmp_egnn_edge_bwd_f32(int64_t n_nodes, int64_t n_edges, int64_t d, const float* pos,

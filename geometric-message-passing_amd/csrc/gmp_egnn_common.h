@@ -67,9 +67,11 @@ template <int D, int NW, bool HF>
 constexpr size_t smem_mats_off() {
   return HF ? smem_carry_off<D, NW, HF>() + (size_t)NW * 4 * carry_stride<D>() : 0;
 }
-template <int D, int NW, bool HF>
+// NMAT = 1 (the variants without the position branch): HF drops the W3 planes, the last of the
+// layout; the f32 layout keeps W3's rows (unfilled) in place
+template <int D, int NW, bool HF, int NMAT = 2>
 constexpr size_t smem_total() {
-  return (HF ? smem_mats_off<D, NW, HF>() + HCfg<D>::MAT
+  return (HF ? smem_mats_off<D, NW, HF>() + (size_t)NMAT * (HCfg<D>::MAT / 2)
              : smem_carry_off<D, NW, HF>() + (size_t)NW * 4 * carry_stride<D>()) * sizeof(float);
 }
 
@@ -88,7 +90,8 @@ __device__ __forceinline__ float act_df(float z) {
 
 // ---------------------------------------------------------------------------------- LDS setup
 // TRANSPOSE (backward): W2^T / W3^T, so the transposed products read 16-byte rows too
-template <int D, bool TRANSPOSE = false>
+// NMAT = 1: W2 only (W3's rows stay unfilled and unread)
+template <int D, bool TRANSPOSE = false, int NMAT = 2>
 __device__ void load_params_to_lds(float* smem, const gmp_egnn_params& P) {
   constexpr int LDW = Cfg<D>::LDW;
   float* sW2 = smem;
@@ -97,15 +100,17 @@ __device__ void load_params_to_lds(float* smem, const gmp_egnn_params& P) {
   for (int i = threadIdx.x; i < D * D / 4; i += blockDim.x) {
     const int o = (4 * i) / D, k = (4 * i) % D;
     const float4 a = reinterpret_cast<const float4*>(P.W2)[i];
-    const float4 b = reinterpret_cast<const float4*>(P.W3)[i];
+    const float4 b = NMAT == 2 ? reinterpret_cast<const float4*>(P.W3)[i] : float4{0.f, 0.f, 0.f, 0.f};
     if (TRANSPOSE) {
       sW2[(k + 0) * LDW + o] = a.x; sW2[(k + 1) * LDW + o] = a.y;
       sW2[(k + 2) * LDW + o] = a.z; sW2[(k + 3) * LDW + o] = a.w;
-      sW3[(k + 0) * LDW + o] = b.x; sW3[(k + 1) * LDW + o] = b.y;
-      sW3[(k + 2) * LDW + o] = b.z; sW3[(k + 3) * LDW + o] = b.w;
+      if (NMAT == 2) {
+        sW3[(k + 0) * LDW + o] = b.x; sW3[(k + 1) * LDW + o] = b.y;
+        sW3[(k + 2) * LDW + o] = b.z; sW3[(k + 3) * LDW + o] = b.w;
+      }
     } else {
       *reinterpret_cast<float4*>(sW2 + o * LDW + k) = a;
-      *reinterpret_cast<float4*>(sW3 + o * LDW + k) = b;
+      if (NMAT == 2) *reinterpret_cast<float4*>(sW3 + o * LDW + k) = b;
     }
   }
   const float* vsrc[NVB] = {P.w1d, P.b1, P.ln1_w, P.ln1_b, P.b2, P.ln2_w,
@@ -143,7 +148,9 @@ __device__ __forceinline__ int clamp_in_exp(int sx, int sw) {
 // after it needs no mean pass (ln_rms).  The backward needs no change: LayerNorm's input gradient
 // has zero mean, so W_c^T dpre = W^T dpre and dW = dpre x^T are the original ones.
 // `scratch` (2 d + 2 floats: the column and bias means) is the carry area, unused until the loop.
-template <int D, bool TRANSPOSE, int CMASK, int ACT>
+// NMAT = 1: W2 alone (no W3 scan, no W3 planes: their LDS is not allocated, smem_total); W2's
+// planes, exponents and the vectors are those of NMAT = 2, bit for bit.
+template <int D, bool TRANSPOSE, int CMASK, int ACT, int NMAT = 2>
 __device__ void load_params_hf(float* sV, _Float16* hW, float* scratch, const gmp_egnn_params& P) {
   using H = HCfg<D>;
   // scalars after the vectors: [0] [1] exponents of W2 / W3, [2] [3] the static (clamped) input
@@ -151,7 +158,7 @@ __device__ void load_params_hf(float* sV, _Float16* hW, float* scratch, const gm
   unsigned* mxw = reinterpret_cast<unsigned*>(sV + NV * D + 4);
   if (threadIdx.x < 6) mxw[threadIdx.x] = 0u;
   __syncthreads();
-  if (threadIdx.x < 2 * D) {  // column (mat, k): mean over the output rows and max |W| (fixed order)
+  if (threadIdx.x < NMAT * D) {  // column (mat, k): mean over the output rows and max |W| (fixed order)
     const int mat = threadIdx.x / D, k = threadIdx.x - mat * D;
     const float* W = mat ? P.W3 : P.W2;
     float s = 0.f, m = 0.f;
@@ -164,7 +171,7 @@ __device__ void load_params_hf(float* sV, _Float16* hW, float* scratch, const gm
     const float mean = ((CMASK >> mat) & 1) ? s * (1.f / D) : 0.f;
     scratch[threadIdx.x] = mean;
     atomicMax(&mxw[mat], __float_as_uint(m + fabsf(mean)));  // >= max |W_c| (a bound suffices)
-  } else if (threadIdx.x < 2 * D + 64) {  // bias means (one wave, fixed-order butterfly)
+  } else if (threadIdx.x >= 2 * D && threadIdx.x < 2 * D + 64) {  // bias means (one wave, fixed-order butterfly)
     const int l = threadIdx.x - 2 * D;
     float a = 0.f, b = 0.f;
     for (int k = l; k < D; k += 64) {
@@ -203,7 +210,7 @@ __device__ void load_params_hf(float* sV, _Float16* hW, float* scratch, const gm
   const int ex3 = clamp_in_exp(scale_exp(rd * __uint_as_float(mxw[4]) + __uint_as_float(mxw[5])), s3);
   __syncthreads();  // (the scratch words are overwritten below)
 #pragma unroll 8
-  for (int i = threadIdx.x; i < 2 * D * D; i += blockDim.x) {
+  for (int i = threadIdx.x; i < NMAT * D * D; i += blockDim.x) {
     const int mat = i / (D * D), e = i - mat * D * D;
     const int o = e / D, k = e - o * D;  // W[o][k]
     const float w = ldexpf((mat ? P.W3 : P.W2)[e] - scratch[mat * D + k], mat ? s3 : s2);
@@ -284,6 +291,11 @@ __device__ __forceinline__ void store_row_w(rsrc_t w, unsigned off, const f32x4 
   for (int p = 0; p < D / 16; ++p)
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, x[p]),
                                            w, off + (16 * p + 4 * g) * 4, 0, AUX);
+}
+template <int AUX>
+__device__ __forceinline__ void store2_w(rsrc_t w, unsigned off, float a, float b) {
+  __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(a), w, off, 0, AUX);
+  __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(b), w, off + 4, 0, AUX);
 }
 template <int AUX>
 __device__ __forceinline__ void store3_w(rsrc_t w, unsigned off, float a, float b, float c) {
@@ -738,10 +750,12 @@ __device__ __forceinline__ int64_t node_begin(const int64_t* __restrict__ rowptr
 }
 
 // carry of the open segment: lane 15 of each group stores, lane 0 of the next chunk adds.
-template <int D>
+// P3 = false: the feature rows alone (no 3-vector riding along)
+template <int D, bool P3 = true>
 __device__ __forceinline__ void carry_store(float* cbuf, const f32x4 (&x)[D / 16], const float (&p3)[3]) {
 #pragma unroll
   for (int p = 0; p < D / 16; ++p) *reinterpret_cast<f32x4*>(cbuf + 4 * p) = x[p];
+  if (!P3) return;
   cbuf[D / 4 + 0] = p3[0];
   cbuf[D / 4 + 1] = p3[1];
   cbuf[D / 4 + 2] = p3[2];
@@ -751,7 +765,7 @@ __device__ __forceinline__ void carry_store(float* cbuf, const f32x4 (&x)[D / 16
 // finite values.  Lanes past the wave's range keep their (finite, clamped-edge) values: they
 // lie after every valid lane of the chunk, so no valid lane's scan reads them, and they never
 // store.
-template <int D>
+template <int D, bool P3 = true>
 __device__ __forceinline__ void carry_apply(const float* cbuf, f32x4 (&x)[D / 16], float (&p3)[3],
                                             bool take) {
   const float tf = take ? 1.f : 0.f;
@@ -761,6 +775,7 @@ __device__ __forceinline__ void carry_apply(const float* cbuf, f32x4 (&x)[D / 16
 #pragma unroll
     for (int q = 0; q < 4; ++q) x[p][q] = __builtin_fmaf(c[q], tf, x[p][q]);
   }
+  if (!P3) return;
 #pragma unroll
   for (int c = 0; c < 3; ++c) p3[c] = __builtin_fmaf(cbuf[D / 4 + c], tf, p3[c]);
 }
@@ -825,12 +840,19 @@ __device__ __forceinline__ EdgeCtx edge_ctx(EdgeIJ ij, int base, int lane_e, int
 // rel = pos_i - pos_j (egnn_layer.py:64), dist = |rel|: called once the chunk's loads are issued.
 // FAST (the HF path, forward and backward alike): v_sqrt_f32 (~1 ulp) instead of the correctly
 // rounded sequence.
-template <bool FAST = false>
+// |rel|^2 is written out with its roundings fixed (no contraction left to the compiler): which
+// products of x^2 + y^2 + z^2 fuse otherwise depends on the other uses of rel in the kernel, so
+// two variants of one kernel (with and without the position branch) got a dist one ulp apart.
+// The two orders are the ones the full d = 128 HF kernels were compiled to before the variants
+// existed (forward: fma(z, z, x^2 + y^2); BWD: fma(y, y, x^2) + z^2), so their results stay put.
+template <bool FAST = false, bool BWD = false>
 __device__ __forceinline__ void edge_geom(EdgeCtx& c) {
+#pragma clang fp contract(off)
   c.rx -= c.pjx;
   c.ry -= c.pjy;
   c.rz -= c.pjz;
-  const float q = c.rx * c.rx + c.ry * c.ry + c.rz * c.rz;
+  const float xx = c.rx * c.rx, yy = c.ry * c.ry, zz = c.rz * c.rz;
+  const float q = BWD ? __builtin_fmaf(c.ry, c.ry, xx) + zz : __builtin_fmaf(c.rz, c.rz, xx + yy);
   c.dist = FAST ? __builtin_amdgcn_sqrtf(q) : sqrtf(q);
 }
 
@@ -886,7 +908,7 @@ __device__ __forceinline__ WaveRange wave_range(const int64_t* __restrict__ rowp
 // each segment end only, so these are the rows it never writes; covering them here replaces
 // two full memsets of the outputs per launch (r04: ~11 us of fill kernels + their boundaries
 // per layer).  The waves' node ranges partition [0, n_nodes).
-template <int D>
+template <int D, bool R3 = true>
 __device__ __forceinline__ void zero_isolated(const WaveRange& wr, const int64_t* __restrict__ rowptr,
                                               float* __restrict__ rows, float* __restrict__ rows3,
                                               int lane) {
@@ -896,9 +918,11 @@ __device__ __forceinline__ void zero_isolated(const WaveRange& wr, const int64_t
       float4* r = reinterpret_cast<float4*>(rows + (size_t)n * D);
 #pragma unroll
       for (int k = 0; k < D / 4; ++k) r[k] = float4{0.f, 0.f, 0.f, 0.f};
-      rows3[3 * (size_t)n] = 0.f;
-      rows3[3 * (size_t)n + 1] = 0.f;
-      rows3[3 * (size_t)n + 2] = 0.f;
+      if (R3) {
+        rows3[3 * (size_t)n] = 0.f;
+        rows3[3 * (size_t)n + 1] = 0.f;
+        rows3[3 * (size_t)n + 2] = 0.f;
+      }
     }
   }
 }

@@ -297,7 +297,7 @@ void egnn_graph_checks(const Tensor& pos, const Tensor& rowptr, const Tensor& re
 std::tuple<Tensor, Tensor, Tensor, Tensor> egnn_edge_fwd(
     const Tensor& AB, const Tensor& pos, const Tensor& rowptr, const Tensor& recv,
     const Tensor& send, const std::vector<Tensor>& params, int64_t act, bool msg_mean, double eps,
-    bool train, int64_t xhat_planes) {
+    bool train, int64_t xhat_planes, bool need_pos) {
   OpGuard g(AB, "egnn_edge_fwd");
   TORCH_CHECK(xhat_planes == 2 || xhat_planes == 3, "gmp.egnn_edge_fwd: xhat_planes is 2 or 3");
   f32(AB, "AB");
@@ -306,23 +306,27 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> egnn_edge_fwd(
               "gmp.egnn_edge_fwd: AB must be (N, 2d)");
   const int64_t N = pos.size(0), E = recv.numel(), d = AB.size(1) / 2;
   gmp_egnn_params P = egnn_params(params, d);
-  Tensor m = at::empty({N, d}, fopt(AB)), pa = at::empty({N, 3}, fopt(AB));
+  // need_pos = false: the message branch alone (GMP_EGNN_NO_POS_BRANCH); pos_aggr has 0 rows and
+  // rstd's third column is not written
+  Tensor m = at::empty({N, d}, fopt(AB)), pa = at::empty({need_pos ? N : 0, 3}, fopt(AB));
   // training: the saved LayerNorm outputs, exactly the planes the forward writes (x_hat1, x_hat2
   // [, x_hat3]); the backward reads their count from xhat.size(0)
   Tensor xh = at::empty({train ? xhat_planes : 0, E, d}, fopt(AB));
   Tensor rs = at::empty({train ? E : 0, 3}, fopt(AB));
-  check_rc(gmp_egnn_edge_fwd_f32(N, E, d, fp(AB), fp(pos), ip(rowptr), ip(recv), ip(send), &P,
-                                 (int)act, msg_mean, (float)eps, fp(m), fp(pa),
-                                 train ? fp(xh) : nullptr, (int)xhat_planes,
-                                 train ? fp(rs) : nullptr, cur_stream()),
-           "gmp_egnn_edge_fwd_f32");
+  check_rc(gmp_egnn_edge_fwd_ex_f32(N, E, d, fp(AB), fp(pos), ip(rowptr), ip(recv), ip(send), &P,
+                                    (int)act, msg_mean, (float)eps, fp(m),
+                                    need_pos ? fp(pa) : nullptr, train ? fp(xh) : nullptr,
+                                    (int)xhat_planes, train ? fp(rs) : nullptr,
+                                    need_pos ? 0u : GMP_EGNN_NO_POS_BRANCH, cur_stream()),
+           "gmp_egnn_edge_fwd_ex_f32");
   return {m, pa, xh, rs};
 }
 
 std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> egnn_edge_bwd(
     const Tensor& pos, const Tensor& rowptr, const Tensor& recv, const Tensor& send,
     const std::vector<Tensor>& params, int64_t act, bool msg_mean, const Tensor& xhat,
-    const Tensor& rstd, const Tensor& g_m, const Tensor& g_p, const optional<Tensor>& amax) {
+    const Tensor& rstd, const Tensor& g_m, const Tensor& g_p, const optional<Tensor>& amax,
+    bool pos_branch, bool pos_grad) {
   OpGuard g(pos, "egnn_edge_bwd");
   egnn_graph_checks(pos, rowptr, recv, send);
   f32(xhat, "xhat");
@@ -336,24 +340,30 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> egnn_edge_bwd
   shape(xhat, {xhat.size(0), E, d}, "xhat");
   shape(rstd, {E, 3}, "rstd");
   shape(g_m, {N, d}, "g_m_aggr");
-  shape(g_p, {N, 3}, "g_pos_aggr");
+  // pos_branch = false (GMP_EGNN_NO_POS_BRANCH): g_pos_aggr is zero by contract and not read (any
+  // f32 tensor, e.g. 0 rows); dpre3 comes back with 0 rows.  pos_grad = false
+  // (GMP_EGNN_NO_POS_GRAD): dpos_recv and gdiff come back with 0 rows.
+  if (pos_branch) shape(g_p, {N, 3}, "g_pos_aggr");
   gmp_egnn_params P = egnn_params(params, d);
   if (amax.has_value()) {
     i32(*amax, "amax");
     TORCH_CHECK(amax->numel() >= 2, "gmp.egnn_edge_bwd: amax has 2 words");
   }
   auto o = fopt(pos);
-  Tensor dA = at::empty({N, d}, o), dpr = at::empty({N, 3}, o), dp1 = at::empty({E, d}, o);
-  Tensor gd = at::empty({E, 3}, o), dp2 = at::empty({E, d}, o), dp3 = at::empty({E, d}, o);
+  Tensor dA = at::empty({N, d}, o), dpr = at::empty({pos_grad ? N : 0, 3}, o);
+  Tensor dp1 = at::empty({E, d}, o), gd = at::empty({pos_grad ? E : 0, 3}, o);
+  Tensor dp2 = at::empty({E, d}, o), dp3 = at::empty({pos_branch ? E : 0, d}, o);
   Tensor part = at::empty({gmp_egnn_edge_bwd_partials_rows(E, d), 8 * d + 1}, o);
-  check_rc(gmp_egnn_edge_bwd_amax_f32(
+  check_rc(gmp_egnn_edge_bwd_ex_f32(
                N, E, d, fp(pos), ip(rowptr), ip(recv), ip(send), &P, (int)act, msg_mean,
-               E > 0 ? fp(xhat) : nullptr, (int)xhat.size(0), fp(rstd), fp(g_m), fp(g_p), fp(dA),
-               fp(dpr), fp(dp1), fp(gd), fp(dp2), fp(dp3), fp(part),
+               E > 0 ? fp(xhat) : nullptr, (int)xhat.size(0), fp(rstd), fp(g_m),
+               pos_branch ? fp(g_p) : nullptr, fp(dA), pos_grad ? fp(dpr) : nullptr, fp(dp1),
+               pos_grad ? fp(gd) : nullptr, fp(dp2), pos_branch ? fp(dp3) : nullptr, fp(part),
                amax.has_value() ? reinterpret_cast<uint32_t*>(amax->data_ptr<int32_t>())
                                 : nullptr,
+               (pos_branch ? 0u : GMP_EGNN_NO_POS_BRANCH) | (pos_grad ? 0u : GMP_EGNN_NO_POS_GRAD),
                cur_stream()),
-           "gmp_egnn_edge_bwd_amax_f32");
+           "gmp_egnn_edge_bwd_ex_f32");
   return {dA, dpr, dp1, gd, dp2, dp3, part};
 }
 
@@ -1653,10 +1663,10 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> egnn_edge_fwd(const Tensor& AB, const
                                                          const Tensor&, const Tensor& recv,
                                                          const Tensor&, const std::vector<Tensor>&,
                                                          int64_t, bool, double, bool train,
-                                                         int64_t xhat_planes) {
+                                                         int64_t xhat_planes, bool need_pos) {
   const int64_t N = pos.size(0), E = recv.numel(), d = AB.size(1) / 2;
   auto o = AB.options();
-  return {at::empty({N, d}, o), at::empty({N, 3}, o),
+  return {at::empty({N, d}, o), at::empty({need_pos ? N : 0, 3}, o),
           at::empty({train ? xhat_planes : 0, E, d}, o), at::empty({train ? E : 0, 3}, o)};
 }
 Tensor egnn_node_image(const std::vector<Tensor>& W0s, const std::vector<Tensor>&,
@@ -1677,11 +1687,12 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> egnn_node_fwd(const Tensor& h, const 
 std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> egnn_edge_bwd(
     const Tensor& pos, const Tensor&, const Tensor& recv, const Tensor&,
     const std::vector<Tensor>&, int64_t, bool, const Tensor& xhat, const Tensor&, const Tensor&,
-    const Tensor&, const optional<Tensor>&) {
+    const Tensor&, const optional<Tensor>&, bool pos_branch, bool pos_grad) {
   const int64_t N = pos.size(0), E = recv.numel(), d = xhat.size(2);
   auto o = pos.options();
-  return {at::empty({N, d}, o), at::empty({N, 3}, o), at::empty({E, d}, o), at::empty({E, 3}, o),
-          at::empty({E, d}, o), at::empty({E, d}, o),
+  return {at::empty({N, d}, o), at::empty({pos_grad ? N : 0, 3}, o), at::empty({E, d}, o),
+          at::empty({pos_grad ? E : 0, 3}, o), at::empty({E, d}, o),
+          at::empty({pos_branch ? E : 0, d}, o),
           at::empty({gmp_egnn_edge_bwd_partials_rows(E, d), 8 * d + 1}, o)};
 }
 Tensor cfconv_aggregate(const Tensor& x, const Tensor&, const Tensor&, const Tensor&,
@@ -1930,7 +1941,8 @@ TORCH_LIBRARY(gmp, m) {
   m.def("segment_reduce_bwd(Tensor grad_out, Tensor index, Tensor rowptr, str reduce, "
         "Tensor? argmax, int n_items) -> Tensor");
   m.def("egnn_edge_fwd(Tensor AB, Tensor pos, Tensor rowptr, Tensor recv, Tensor send, "
-        "Tensor[] params, int act, bool msg_mean, float eps, bool train, int xhat_planes=2) -> "
+        "Tensor[] params, int act, bool msg_mean, float eps, bool train, int xhat_planes=2, "
+        "bool need_pos=True) -> "
         "(Tensor m_aggr, Tensor pos_aggr, Tensor xhat, Tensor rstd)");
   m.def("egnn_node_image(Tensor[] W0s, Tensor[] W3s, Tensor?[] W1ns) -> Tensor");
   m.def("egnn_node_fwd(Tensor h, Tensor m_aggr, Tensor[] vecs, Tensor image, bool with_ab, "
@@ -1938,7 +1950,8 @@ TORCH_LIBRARY(gmp, m) {
         "Tensor xhat, Tensor rstd)");
   m.def("egnn_edge_bwd(Tensor pos, Tensor rowptr, Tensor recv, Tensor send, Tensor[] params, "
         "int act, bool msg_mean, Tensor xhat, Tensor rstd, Tensor g_m_aggr, Tensor g_pos_aggr, "
-        "Tensor(a!)? amax=None) -> (Tensor dA, Tensor dpos_recv, "
+        "Tensor(a!)? amax=None, bool pos_branch=True, bool pos_grad=True) -> (Tensor dA, "
+        "Tensor dpos_recv, "
         "Tensor dpre1, Tensor gdiff, Tensor dpre2, Tensor dpre3, Tensor partials)");
   m.def("cfconv_aggregate(Tensor x, Tensor xidx, Tensor w, Tensor perm, Tensor rowptr, "
         "int n_seg, Tensor? escale=None) -> Tensor");

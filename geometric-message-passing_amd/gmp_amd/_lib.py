@@ -23,6 +23,8 @@ c_size = ctypes.c_size_t
 GMP_OK, GMP_ERR_ARG, GMP_ERR_HIP, GMP_ERR_UNSUPPORTED, GMP_ERR_WORKSPACE = 0, -1, -2, -3, -4
 REDUCE = {"sum": 0, "add": 0, "mean": 1, "max": 2}
 ACT = {"relu": 0, "swish": 1, "silu": 1}
+# flags of gmp_egnn_edge_{fwd,bwd}_ex_f32 (include/gmp.h GMP_EGNN_*)
+EGNN_NO_POS_BRANCH, EGNN_NO_POS_GRAD = 1, 2
 
 
 class GmpEgnnParams(ctypes.Structure):
@@ -207,6 +209,13 @@ SIGNATURES = {
     # second-order (energy-and-force) kernels; additions only, the ABI version is unchanged
     "gmp_cfconv_cgrad_f32": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64,
                                      c_i64, c_vp, c_vp, c_vp]),
+    # K4 with a flags word (EGNN_NO_POS_BRANCH / EGNN_NO_POS_GRAD below); additions only
+    "gmp_egnn_edge_fwd_ex_f32": (c_int, [c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                         ctypes.POINTER(GmpEgnnParams), c_int, c_int, c_f32, c_vp,
+                                         c_vp, c_vp, c_int, c_vp, ctypes.c_uint32, c_vp]),
+    "gmp_egnn_edge_bwd_ex_f32": (c_int, [c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp,
+                                         ctypes.POINTER(GmpEgnnParams), c_int, c_int, c_vp, c_int]
+                                 + [c_vp] * 11 + [ctypes.c_uint32, c_vp]),
     "gmp_ssp_bwd2_f32": (c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "gmp_schnet_featurize_bwd2_f32": (c_int, [c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_f32, c_f32]
                                       + [c_vp] * 9),

@@ -67,9 +67,10 @@ class EGNNLayer(MessagePassing):
                 and h.dtype == torch.float32 and pos.dtype == torch.float32
                 and all(ln.elementwise_affine and ln.eps == lns[0].eps for ln in lns))
 
-    def fused_message(self, edge_index, h, pos, AB=None):
+    def fused_message(self, edge_index, h, pos, AB=None, need_pos=True):
         """(m_aggr, pos_aggr) of the fused message block (K4); AB: the node projections when the
-        previous layer's K15 update produced them."""
+        previous layer's K15 update produced them.  need_pos=False: the caller drops the position
+        output — (m_aggr, None), and the kernels leave the mlp_pos branch out."""
         graph = ops.egnn_graph(edge_index, h.shape[0])
         m0, ln1, m3, ln2 = self.mlp_msg[0], self.mlp_msg[1], self.mlp_msg[3], self.mlp_msg[4]
         p0, ln3, p3 = self.mlp_pos[0], self.mlp_pos[1], self.mlp_pos[3]
@@ -77,7 +78,7 @@ class EGNNLayer(MessagePassing):
             h, pos, graph, self.activation_name, self.aggr == "mean", ln1.eps,
             m0.weight, m0.bias, ln1.weight, ln1.bias, m3.weight, m3.bias, ln2.weight, ln2.bias,
             p0.weight, p0.bias, ln3.weight, ln3.bias, p3.weight, p3.bias, torch.is_grad_enabled(),
-            AB)
+            AB, need_pos)
 
     def fused_propagate(self, edge_index, h, pos):
         m_aggr, p_aggr = self.fused_message(edge_index, h, pos)
@@ -158,9 +159,12 @@ class EGNNModel(nn.Module):
                 table = self.emb_in.weight.mm(torch.cat([W1[:, :d], W1[:, d:2 * d]], 0).t())
                 AB = ops.gather_rows(table, batch.atoms)
             for k, conv in enumerate(convs):
-                m_aggr, p_aggr = conv.fused_message(batch.edge_index, h, pos, AB)
+                # the last layer's positions are read only by the equivariant readout
+                need_pos = self.equivariant_pred or nexts[k] is not None
+                m_aggr, p_aggr = conv.fused_message(batch.edge_index, h, pos, AB, need_pos)
                 h, AB = conv.fused_update(h, m_aggr, nexts[k], self.residual, images[k])
-                pos = pos + p_aggr
+                if need_pos:
+                    pos = pos + p_aggr
         else:
             for conv in self.convs:
                 h_update, pos = conv(h, pos, batch.edge_index)

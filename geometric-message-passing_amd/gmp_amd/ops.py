@@ -771,6 +771,13 @@ def _egnn_params(tensors):
 # The backward follows the saved tensor's plane count.
 EGNN_XHAT_PLANES = 2
 
+# True: EgnnMessageFn leaves out the work nobody reads — the mlp_pos branch of a layer whose
+# position output is unused (need_pos=False in the forward; in the backward whenever no gradient
+# arrives for pos_aggr: kernels without the W3 products, no dW3 / db3 outer sum) and the position
+# gradient when pos does not require grad (no gdiff, no sender-side reduction).  Results are
+# bitwise those of False, which runs the full kernels everywhere (the A/B and the tests).
+EGNN_SKIP_DEAD_POS = True
+
 
 class EgnnMessageFn(torch.autograd.Function):
     """The whole EGNN message block of one layer (egnn_layer.py:62-80 with the MLPs of :28-36):
@@ -782,14 +789,16 @@ class EgnnMessageFn(torch.autograd.Function):
     Parameters in module order: mlp_msg.0.{weight (d, 2d+1), bias}, mlp_msg.1.{weight, bias},
     mlp_msg.3.{weight, bias}, mlp_msg.4.{weight, bias}, mlp_pos.0.{weight, bias},
     mlp_pos.1.{weight, bias}, mlp_pos.3.{weight (1, d), bias}.
-    Returns (m_aggr (N, d), pos_aggr (N, 3)).  AB: the node projections precomputed by the
+    Returns (m_aggr (N, d), pos_aggr (N, 3)); need_pos=False (the caller drops this layer's
+    position output, e.g. the model's last layer without equivariant_pred): (m_aggr, None), and
+    mlp_pos receives zero gradients.  AB: the node projections precomputed by the
     previous layer's K15 node update (EgnnNodeFn), a constant here: the gradient w.r.t. h still
     comes from this Function's backward (dh = [dA | dB] [W1a ; W1b]).
     """
 
     @staticmethod
     def forward(ctx, h, pos, graph, act, msg_mean, eps, W1, b1, ln1w, ln1b, W2, b2, ln2w, ln2b,
-                W3, b3, ln3w, ln3b, w4, b4, grad_mode=True, AB=None):
+                W3, b3, ln3w, ln3b, w4, b4, grad_mode=True, AB=None, need_pos=True):
         h, pos = _f32c(h), _f32c(pos)
         _need_cuda(h, pos, W1)
         N, d = h.shape
@@ -804,14 +813,18 @@ class EgnnMessageFn(torch.autograd.Function):
         # needs_input_grad follows requires_grad alone: r04's inference forward saved 1 GB of
         # x_hat planes per layer under torch.no_grad)
         train = bool(grad_mode) and any(ctx.needs_input_grad)
+        # a None g_p in backward then means that nobody used the position output
+        ctx.set_materialize_grads(False)
+        fwd_pos = bool(need_pos) or not EGNN_SKIP_DEAD_POS
         with _timed("egnn_edge_fwd"):
             m_aggr, pos_aggr, xhat, rstd = _lib.torch_ops().egnn_edge_fwd(
                 AB, pos, graph.rowptr, graph.recv, graph.send, list(params), _lib.ACT[act],
-                bool(msg_mean), float(eps), train, EGNN_XHAT_PLANES)
+                bool(msg_mean), float(eps), train, EGNN_XHAT_PLANES, fwd_pos)
         ctx.graph, ctx.act, ctx.msg_mean, ctx.N = graph, act, msg_mean, N
+        ctx.fwd_pos = fwd_pos  # False: rstd[:, 2] (and x_hat3) were not written
         if train:
             ctx.save_for_backward(h, pos, xhat, rstd, W1, *params)
-        return m_aggr, pos_aggr
+        return m_aggr, (pos_aggr if need_pos else None)
 
     @staticmethod
     @once_differentiable
@@ -821,9 +834,16 @@ class EgnnMessageFn(torch.autograd.Function):
         N, d = ctx.N, xhat.shape[2]
         E = graph.num_edges
         dev = pos.device
-        g_m = torch.zeros((N, d), device=dev) if g_m is None else _f32c(g_m)
-        g_p = torch.zeros((N, 3), device=dev) if g_p is None else _f32c(g_p)
         f = dict(dtype=torch.float32, device=dev)
+        # static per call site (no data-dependent branch): the position branch only where it ran
+        # in the forward and a gradient arrives for it; the position gradient only where asked for
+        pos_branch = ctx.fwd_pos and not (EGNN_SKIP_DEAD_POS and g_p is None)
+        pos_grad = ctx.needs_input_grad[1] or not EGNN_SKIP_DEAD_POS
+        g_m = torch.zeros((N, d), **f) if g_m is None else _f32c(g_m)
+        if not pos_branch:
+            g_p = torch.empty((0, 3), **f)  # (not read)
+        else:
+            g_p = torch.zeros((N, 3), **f) if g_p is None else _f32c(g_p)
         # HF weight-gradient outer sums: the backward kernel folds max |dpre2|, |dpre3| into
         # two device words that scale their fp16 planes
         amax = torch.zeros(2, dtype=torch.int32, device=dev)
@@ -831,15 +851,18 @@ class EgnnMessageFn(torch.autograd.Function):
             dA, dpos_recv, dpre1, gdiff, dpre2, dpre3, partials = \
                 _lib.torch_ops().egnn_edge_bwd(pos, graph.rowptr, graph.recv, graph.send,
                                                list(params), _lib.ACT[ctx.act],
-                                               bool(ctx.msg_mean), xhat, rstd, g_m, g_p, amax)
+                                               bool(ctx.msg_mean), xhat, rstd, g_m, g_p, amax,
+                                               pos_branch, pos_grad)
         xh1, xh2 = xhat[0], xhat[1]  # for the dW2 / dW3 sums
         # critical path: sender-side sums (deterministic, sender CSR) and dh
         dB, _ = segment_reduce(dpre1, graph.send_csr, "sum")
-        dpos_send, _ = segment_reduce(gdiff, graph.send_csr, "sum")
         W1t = W1[:, :2 * d].t().contiguous()  # [W1a | W1b]^T: NT-form GEMMs for dh
         dh = _mm_wt(dA, W1t[:d])
         dh.addmm_(dB, W1t[d:].t())
-        dpos = dpos_recv - dpos_send
+        dpos = None
+        if pos_grad:
+            dpos_send, _ = segment_reduce(gdiff, graph.send_csr, "sum")
+            dpos = dpos_recv - dpos_send
 
         # weight gradients: side stream, accumulated at the end of the backward pass
         (_, b1, ln1w, ln1b, W2, b2, ln2w, ln2b, W3, b3, ln3w, ln3b, w4, b4) = params
@@ -848,7 +871,10 @@ class EgnnMessageFn(torch.autograd.Function):
         # (LayerNorm backward + its column sums 0.33 ms instead of ~0.04 ms per layer, trace);
         # A/B on one box, 20-step runs: 114.4 (113.7-115.0) vs 113.2 (112.9-113.4) M edges/s
         dW2, db2 = edge_outer_sum_act(dpre2, xh1, ln1w, ln1b, ctx.act, amax[0:1])
-        dW3, db3 = edge_outer_sum_act(dpre3, xh2, ln2w, ln2b, ctx.act, amax[1:2])
+        if pos_branch:
+            dW3, db3 = edge_outer_sum_act(dpre3, xh2, ln2w, ln2b, ctx.act, amax[1:2])
+        else:  # the loss reaches none of mlp_pos: zeros, what the sum of a zero dpre3 gave
+            dW3, db3 = torch.zeros((d, d), **f), torch.zeros(d, **f)
         with side_work(h, dA, dB, partials) as sw:
             dW1 = torch.empty((d, 2 * d + 1), **f)
             db1 = torch.empty(d, **f)
@@ -863,7 +889,7 @@ class EgnnMessageFn(torch.autograd.Function):
         # then b1 ... b4 (params[0] is the contiguous copy of W1's distance column)
         targets = (W1,) + tuple(params[1:])
         return (dh, dpos, None, None, None, None) + sw.deliver(ctx.needs_input_grad, 6, targets,
-                                                               grads) + (None, None)
+                                                               grads) + (None, None, None)
 
 
 def egnn_exact_mode():

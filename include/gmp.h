@@ -146,6 +146,24 @@ int gmp_egnn_edge_fwd_f32(int64_t n_nodes, int64_t n_edges, int64_t d, const flo
                           const int64_t* send, const gmp_egnn_params* params, int act,
                           int msg_mean, float ln_eps, float* m_aggr, float* pos_aggr,
                           float* save_xhat, int save_planes, float* save_rstd, void* stream);
+/* Flags of the _ex entry points (0: the forms above).
+ * GMP_EGNN_NO_POS_BRANCH: nobody reads this layer's position output (egnn.py's last layer
+ *   without equivariant_pred).  Forward: mlp_pos is not evaluated — no W3 product, LN3 or w4 dot;
+ *   pos_aggr (may be NULL) and column 2 of save_rstd are not written; m_aggr, save_xhat's first
+ *   two planes and save_rstd[:, 0:2] are bitwise those of flags = 0.  Backward: g_pos_aggr is
+ *   taken as zero (g_pos_aggr, dpre3 may be NULL; x_hat3 and save_rstd[:, 2] are not read); the
+ *   ln3_w / ln3_b / w4 / b4 slots of vec_partials are zeros, amax[1] is left alone, every other
+ *   output is bitwise that of flags = 0 with a zero g_pos_aggr.
+ * GMP_EGNN_NO_POS_GRAD (backward only): the caller wants no gradient w.r.t. pos; dpos_recv and
+ *   gdiff (may be NULL) are not written, every other output unchanged. */
+#define GMP_EGNN_NO_POS_BRANCH 1u
+#define GMP_EGNN_NO_POS_GRAD 2u
+int gmp_egnn_edge_fwd_ex_f32(int64_t n_nodes, int64_t n_edges, int64_t d, const float* AB,
+                             const float* pos, const int64_t* rowptr, const int64_t* recv,
+                             const int64_t* send, const gmp_egnn_params* params, int act,
+                             int msg_mean, float ln_eps, float* m_aggr, float* pos_aggr,
+                             float* save_xhat, int save_planes, float* save_rstd, uint32_t flags,
+                             void* stream);
 
 /* K15 (r05): the EGNN node update of one layer and the next layer's node projections in one
  * launch — replaces egnn_layer.py:82-86 (update: mlp_upd(cat([h, m_aggr]))), egnn.py:75-76 (the
@@ -234,6 +252,15 @@ int gmp_egnn_edge_bwd_amax_f32(int64_t n_nodes, int64_t n_edges, int64_t d, cons
                                const float* g_m_aggr, const float* g_pos_aggr, float* dA,
                                float* dpos_recv, float* dpre1, float* gdiff, float* dpre2,
                                float* dpre3, float* vec_partials, uint32_t* amax, void* stream);
+/* As gmp_egnn_edge_bwd_amax_f32 (amax may be NULL) with the GMP_EGNN_* flags above. */
+int gmp_egnn_edge_bwd_ex_f32(int64_t n_nodes, int64_t n_edges, int64_t d, const float* pos,
+                             const int64_t* rowptr, const int64_t* recv, const int64_t* send,
+                             const gmp_egnn_params* params, int act, int msg_mean,
+                             const float* save_xhat, int save_planes, const float* save_rstd,
+                             const float* g_m_aggr, const float* g_pos_aggr, float* dA,
+                             float* dpos_recv, float* dpre1, float* gdiff, float* dpre2,
+                             float* dpre3, float* vec_partials, uint32_t* amax, uint32_t flags,
+                             void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Edge-reduction GEMM for per-edge Linear weight gradients (egnn_layer.py:28-39 mlp_msg /
