@@ -724,6 +724,18 @@ int64_t x3_blocks_for(int64_t K) {
   if (g * min_per > K) g = ceil_div(K, min_per);
   return g < 1 ? 1 : g;
 }
+int64_t x3_units(int64_t m, int64_t n) { return ((2 * m + 63) & ~63) + ((2 * n + 63) & ~63); }
+// Does the split-plane kernel take (K, m, n)?  Host arithmetic only.
+// Narrow products (m n < 4096) stay on the f32-MFMA kernels: too little matrix work per
+// loaded byte for the split's VALU and LDS staging to pay (measured: 16 x 128, 48 x 48 slower).
+// Node-level sums (K ~ 50k rows) stay there too: a few stages per block, and the 1-block-per-
+// CU LDS footprint keeps them from sharing CUs with the concurrent main-stream kernels.
+bool x3_ok(int64_t K, int64_t m, int64_t n) {
+  if (m * n < 4096 || K < kX3MinK) return false;
+  int wn = 0;
+  if (x3_pick(m, n, &wn) < 0 || m + n + kXPad > 416) return false;  // 2 x 3 x (R + pad) x 64 B
+  return x3_units(m, n) <= 2 * kXT;
+}
 
 // C (m x n, row stride ldc) = A^T pro(B), colsum(A): split-K over x3 blocks + ordered sums.
 // Returns GMP_ERR_UNSUPPORTED for shapes outside the compiled tilings.
@@ -735,18 +747,12 @@ int outer_sum_x3_launch(int64_t K, int64_t m, int64_t n, const float* A, int64_t
   const bool hf = amaxA != nullptr;  // HF form: act prologue (pro != 0), single B operand
   if (hf && (pro == 0 || B2 || n > kXT)) return GMP_ERR_UNSUPPORTED;
   if (n1 < 0) n1 = n;  // single B operand
-  // Narrow products (m n < 4096) stay on the f32-MFMA kernels: too little matrix work per
-  // loaded byte for the split's VALU and LDS staging to pay (measured: 16 x 128, 48 x 48 slower).
-  // Node-level sums (K ~ 50k rows) stay there too: a few stages per block, and the 1-block-per-
-  // CU LDS footprint keeps them from sharing CUs with the concurrent main-stream kernels.
-  if (m * n < 4096 || K < kX3MinK) return GMP_ERR_UNSUPPORTED;
+  if (!x3_ok(K, m, n)) return GMP_ERR_UNSUPPORTED;
   int wn = 0;
   const int shape = x3_pick(m, n, &wn);
   const int64_t R = m + n;
-  if (shape < 0 || R + kXPad > 416) return GMP_ERR_UNSUPPORTED;  // 2 x 3 x (R + pad) x 64 B
   GMP_CHECK_ARG(pro == 0 || ((reinterpret_cast<uintptr_t>(bw) | reinterpret_cast<uintptr_t>(bb)) % 16 == 0));
-  const int64_t units = ((2 * m + 63) & ~63) + ((2 * n + 63) & ~63);
-  if (units > 2 * kXT) return GMP_ERR_UNSUPPORTED;
+  const int64_t units = x3_units(m, n);
   const int nl = units <= kXT ? 1 : 2;
   const int64_t G = x3_blocks_for(K);
   const int64_t per = ceil_div(ceil_div(K, G), kXK) * kXK;
@@ -1208,6 +1214,41 @@ int64_t blocks_for(int64_t K) {
   return g < 1 ? 1 : g;
 }
 
+// The route of one outer sum: which kernel (or none) takes (K, m, n) with these strides in the
+// current gmp_wgrad_set_f32_mfma mode.  Host arithmetic only (no HIP call, no pointers): the
+// launch functions switch on the value and gmp_edge_outer_sum_ex_route reports it, so the
+// decision is written once.  GMP_ERR_ARG for invalid sizes or strides.
+// Square form, d in {32, 64, 128} (the caller checks d), pro = act + 1.
+int square_route(int64_t K, int64_t d, int64_t lda, int64_t ldb, int pro) {
+  if (!(K >= 0 && pro >= 0 && pro <= 2)) return GMP_ERR_ARG;
+  if (!(lda >= d && ldb >= d && lda % 4 == 0 && ldb % 4 == 0)) return GMP_ERR_ARG;
+  if (K == 0) return GMP_WGRAD_ROUTE_ZERO;
+  if (!wgrad_f32_mfma() && x3_ok(K, d, d)) return GMP_WGRAD_ROUTE_X3;
+  if (quad_ok(K, d, d, pro, lda, ldb) && d >= 64) return GMP_WGRAD_ROUTE_QUAD;
+  return GMP_WGRAD_ROUTE_SQUARE_F32;
+}
+// Rectangular form (no activation prologue).  Every valid shape has a route: where neither a
+// tile bucket (m <= kT) nor the quadrant kernel covers it, the library GEMM, K = 0 included.
+int rect_route(int64_t K, int64_t m, int64_t n, int64_t lda, int64_t ldb) {
+  if (!(K >= 0 && m > 0 && n > 0 && m % 16 == 0 && n % 16 == 0)) return GMP_ERR_ARG;
+  if (!(lda >= m && ldb >= n && lda % 4 == 0 && ldb % 4 == 0)) return GMP_ERR_ARG;
+  const bool bucket = m <= kT && rect_bucket(m, n) != 0;
+  const bool quad = quad_ok(K, m, n, 0, lda, ldb);
+  if (!bucket && !quad) return GMP_WGRAD_ROUTE_LIBRARY;
+  if (K == 0) return GMP_WGRAD_ROUTE_ZERO;
+  if (!wgrad_f32_mfma() && x3_ok(K, m, n)) return GMP_WGRAD_ROUTE_X3;
+  return quad ? GMP_WGRAD_ROUTE_QUAD : GMP_WGRAD_ROUTE_RECT_F32;
+}
+bool square_dim(int64_t m, int64_t n) { return m == n && (m == 32 || m == 64 || m == 128); }
+// gmp_edge_outer_sum_ex_f32's: the square kernel's shapes go there, with or without the
+// activation prologue; the prologue exists for those shapes only.
+int ex_route(int64_t K, int64_t m, int64_t n, int64_t lda, int64_t ldb, int act) {
+  if (!(act >= -1 && act <= 1)) return GMP_ERR_ARG;
+  if (square_dim(m, n)) return square_route(K, m, lda, ldb, act + 1);
+  if (act != -1) return GMP_WGRAD_ROUTE_LIBRARY;
+  return rect_route(K, m, n, lda, ldb);
+}
+
 }  // namespace
 }  // namespace gmp
 
@@ -1233,10 +1274,11 @@ static int outer_sum_launch(int64_t K, int64_t d, const float* A, int64_t lda, c
                             int64_t ldc, float* colsum_A, void* workspace, size_t workspace_bytes,
                             void* stream) {
   if (!(d == 32 || d == 64 || d == 128)) return GMP_ERR_UNSUPPORTED;
-  GMP_CHECK_ARG(K >= 0 && C && pro >= 0 && pro <= 2 && (pro == 0 || (bw && bb)));
-  GMP_CHECK_ARG(lda >= d && ldb >= d && ldc >= d && lda % 4 == 0 && ldb % 4 == 0);
+  const int route = square_route(K, d, lda, ldb, pro);
+  if (route < 0) return route;
+  GMP_CHECK_ARG(C && ldc >= d && (pro == 0 || (bw && bb)));
   hipStream_t s = as_stream(stream);
-  if (K == 0) {
+  if (route == GMP_WGRAD_ROUTE_ZERO) {
     int rc = hip_check(hipMemset2DAsync(C, ldc * sizeof(float), 0, d * sizeof(float), d, s));
     if (!rc && colsum_A) rc = hip_check(hipMemsetAsync(colsum_A, 0, d * sizeof(float), s));
     return rc;
@@ -1246,13 +1288,10 @@ static int outer_sum_launch(int64_t K, int64_t d, const float* A, int64_t lda, c
   GMP_CHECK_ARG(pro == 0 || (reinterpret_cast<uintptr_t>(bw) % 16 == 0 &&
                              reinterpret_cast<uintptr_t>(bb) % 16 == 0));
   if (workspace_bytes < gmp_edge_outer_sum_workspace_size(K, d)) return GMP_ERR_WORKSPACE;
-  if (!wgrad_f32_mfma()) {
-    const int rc = outer_sum_x3_launch(K, d, d, A, lda, B, ldb, pro, bw, bb, C, ldc, colsum_A,
-                                       workspace, s);
-    if (rc != GMP_ERR_UNSUPPORTED) return rc;
-  }
-  if (quad_ok(K, d, d, pro, lda, ldb) && d >= 64 &&
-      reinterpret_cast<uintptr_t>(A) % 16 == 0 && reinterpret_cast<uintptr_t>(B) % 16 == 0)
+  if (route == GMP_WGRAD_ROUTE_X3)
+    return outer_sum_x3_launch(K, d, d, A, lda, B, ldb, pro, bw, bb, C, ldc, colsum_A,
+                               workspace, s);
+  if (route == GMP_WGRAD_ROUTE_QUAD)
     return outer_sum_quad_launch(K, d, d, A, lda, B, ldb, C, ldc, colsum_A, workspace, s);
   const int64_t G = blocks_for(K);
   const int64_t per = ceil_div(ceil_div(K, G), kKT) * kKT;
@@ -1333,13 +1372,12 @@ static int outer_sum_rect_launch(int64_t K, int64_t m, int64_t n, const float* A
                                  const float* B, int64_t ldb, float* C, int64_t ldc,
                                  float* colsum_A, void* workspace, size_t workspace_bytes,
                                  void* stream) {
-  GMP_CHECK_ARG(K >= 0 && C && m > 0 && n > 0 && m % 16 == 0 && n % 16 == 0);
-  GMP_CHECK_ARG(lda >= m && ldb >= n && ldc >= n && lda % 4 == 0 && ldb % 4 == 0);
-  GMP_CHECK_ARG(m <= kT || quad_ok(K, m, n, 0, lda, ldb));
-  const int bucket = m <= kT ? rect_bucket(m, n) : 0;
-  if (!bucket && !quad_ok(K, m, n, 0, lda, ldb)) return GMP_ERR_UNSUPPORTED;
+  const int route = rect_route(K, m, n, lda, ldb);
+  if (route < 0) return route;
+  if (route == GMP_WGRAD_ROUTE_LIBRARY) return GMP_ERR_UNSUPPORTED;
+  GMP_CHECK_ARG(C && ldc >= n);
   hipStream_t s = as_stream(stream);
-  if (K == 0) {
+  if (route == GMP_WGRAD_ROUTE_ZERO) {
     int rc = hip_check(hipMemset2DAsync(C, ldc * sizeof(float), 0, n * sizeof(float), m, s));
     if (!rc && colsum_A) rc = hip_check(hipMemsetAsync(colsum_A, 0, m * sizeof(float), s));
     return rc;
@@ -1347,14 +1385,12 @@ static int outer_sum_rect_launch(int64_t K, int64_t m, int64_t n, const float* A
   GMP_CHECK_ARG(A && B && workspace);
   GMP_CHECK_ARG(reinterpret_cast<uintptr_t>(A) % 16 == 0 && reinterpret_cast<uintptr_t>(B) % 16 == 0);
   if (workspace_bytes < gmp_edge_outer_sum_rect_workspace_size(K, m, n)) return GMP_ERR_WORKSPACE;
-  if (!wgrad_f32_mfma()) {
-    const int rc2 = outer_sum_x3_launch(K, m, n, A, lda, B, ldb, 0, nullptr, nullptr, C, ldc,
-                                        colsum_A, workspace, s);
-    if (rc2 != GMP_ERR_UNSUPPORTED) return rc2;
-  }
-  if (quad_ok(K, m, n, 0, lda, ldb))
+  if (route == GMP_WGRAD_ROUTE_X3)
+    return outer_sum_x3_launch(K, m, n, A, lda, B, ldb, 0, nullptr, nullptr, C, ldc, colsum_A,
+                               workspace, s);
+  if (route == GMP_WGRAD_ROUTE_QUAD)
     return outer_sum_quad_launch(K, m, n, A, lda, B, ldb, C, ldc, colsum_A, workspace, s);
-  if (!bucket) return GMP_ERR_UNSUPPORTED;
+  const int bucket = rect_bucket(m, n);  // RECT_F32: m <= kT and a compiled bucket
   const int64_t G = rect_blocks_for(K);
   const int64_t per = ceil_div(ceil_div(K, G), kKT) * kKT;
   const int64_t Gr = ceil_div(K, per);
@@ -1405,8 +1441,16 @@ int gmp_edge_outer_sum_rect_f32(int64_t K, int64_t m, int64_t n, const float* A,
 }
 
 size_t gmp_edge_outer_sum_ex_workspace_size(int64_t K, int64_t m, int64_t n) {
-  if (m == n && (m == 32 || m == 64 || m == 128)) return gmp_edge_outer_sum_workspace_size(K, m);
+  if (square_dim(m, n)) return gmp_edge_outer_sum_workspace_size(K, m);
+  // no kernel, no partial slabs (the route of a valid call does not depend on its strides)
+  const int route = rect_route(K, m, n, m, n);
+  if (route < 0 || route == GMP_WGRAD_ROUTE_LIBRARY) return 0;
   return gmp_edge_outer_sum_rect_workspace_size(K, m, n);
+}
+
+int gmp_edge_outer_sum_ex_route(int64_t K, int64_t m, int64_t n, int64_t lda, int64_t ldb,
+                                int act) {
+  return ex_route(K, m, n, lda, ldb, act);
 }
 
 int gmp_edge_outer_sum_ex2_f32(int64_t K, int64_t m, int64_t n1, int64_t n2, const float* A,
@@ -1431,11 +1475,12 @@ int gmp_edge_outer_sum_ex_f32(int64_t K, int64_t m, int64_t n, const float* A, i
                               const float* B, int64_t ldb, int act, const float* w, const float* b,
                               float* C, int64_t ldc, float* colsum_A, void* workspace,
                               size_t workspace_bytes, void* stream) {
-  GMP_CHECK_ARG(act >= -1 && act <= 1);
-  if (m == n && (m == 32 || m == 64 || m == 128))
+  const int route = ex_route(K, m, n, lda, ldb, act);
+  if (route < 0) return route;
+  if (route == GMP_WGRAD_ROUTE_LIBRARY) return GMP_ERR_UNSUPPORTED;
+  if (square_dim(m, n))
     return outer_sum_launch(K, m, A, lda, B, ldb, act + 1, w, b, C, ldc, colsum_A, workspace,
                             workspace_bytes, stream);
-  if (act != -1) return GMP_ERR_UNSUPPORTED;  // activation prologue: square shapes only
   return outer_sum_rect_launch(K, m, n, A, lda, B, ldb, C, ldc, colsum_A, workspace,
                                workspace_bytes, stream);
 }

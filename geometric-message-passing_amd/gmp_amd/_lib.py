@@ -25,6 +25,9 @@ REDUCE = {"sum": 0, "add": 0, "mean": 1, "max": 2}
 ACT = {"relu": 0, "swish": 1, "silu": 1}
 # flags of gmp_egnn_edge_{fwd,bwd}_ex_f32 (include/gmp.h GMP_EGNN_*)
 EGNN_NO_POS_BRANCH, EGNN_NO_POS_GRAD = 1, 2
+# gmp_edge_outer_sum_ex_route (include/gmp.h GMP_WGRAD_ROUTE_*)
+(WGRAD_ROUTE_ZERO, WGRAD_ROUTE_X3, WGRAD_ROUTE_QUAD, WGRAD_ROUTE_SQUARE_F32,
+ WGRAD_ROUTE_RECT_F32, WGRAD_ROUTE_LIBRARY) = range(1, 7)
 
 
 class GmpEgnnParams(ctypes.Structure):
@@ -134,6 +137,8 @@ SIGNATURES = {
     "gmp_edge_outer_sum_ex2_f32": (c_int, [c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64,
                                            c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_size, c_vp]),
     "gmp_edge_outer_sum_ex_workspace_size": (c_size, [c_i64, c_i64, c_i64]),
+    # the route query (host arithmetic only); an addition, the ABI version is unchanged
+    "gmp_edge_outer_sum_ex_route": (c_int, [c_i64, c_i64, c_i64, c_i64, c_i64, c_int]),
     "gmp_edge_outer_sum_ex_f32": (c_int, [c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_int,
                                           c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_size, c_vp]),
     "gmp_edge_outer_sum_rect_workspace_size": (c_size, [c_i64, c_i64, c_i64]),

@@ -733,17 +733,23 @@ class GVPConvLayer(nn.Module):
         self.residual = residual
 
     def forward(self, x, edge_index, edge_attr, autoregressive_x=None, node_mask=None):
+        xc = x
+        if node_mask is not None and torch.is_grad_enabled():
+            # the masked rows are written back into x in place below, while the conv's node
+            # projections keep their input for the weight gradients: they get their own copy
+            # (the reference's conv gathers rows and keeps none, so its backward runs)
+            xc = x[0].clone(), x[1].clone()
         if autoregressive_x is not None:
             src, dst = edge_index
             mask = src < dst
-            dh = tuple_sum(self.conv(x, edge_index[:, mask], tuple_index(edge_attr, mask)),
+            dh = tuple_sum(self.conv(xc, edge_index[:, mask], tuple_index(edge_attr, mask)),
                            self.conv(autoregressive_x, edge_index[:, ~mask],
                                      tuple_index(edge_attr, ~mask)))
             count = ops.get_csr(dst, dh[0].size(0)).counts().clamp(min=1).unsqueeze(-1)
             count = count.to(dh[0].dtype)
             dh = dh[0] / count, dh[1] / count.unsqueeze(-1)
         else:
-            dh = self.conv(x, edge_index, edge_attr)
+            dh = self.conv(xc, edge_index, edge_attr)
         if node_mask is not None:
             x_ = x
             x, dh = tuple_index(x, node_mask), tuple_index(dh, node_mask)

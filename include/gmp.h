@@ -328,6 +328,23 @@ int gmp_edge_outer_sum_ex2_f32(int64_t K, int64_t m, int64_t n1, int64_t n2, con
                                int64_t ldb2, float* C, int64_t ldc, float* colsum_A,
                                void* workspace, size_t workspace_bytes, void* stream);
 size_t gmp_edge_outer_sum_ex_workspace_size(int64_t K, int64_t m, int64_t n);
+/* Which kernel gmp_edge_outer_sum_ex_f32 runs for these sizes and strides in the current
+ * gmp_wgrad_set_f32_mfma mode: host arithmetic only, no HIP call, and the very decision the
+ * launch takes.  GMP_ERR_ARG for invalid arguments (valid: K >= 0, m and n positive multiples
+ * of 16, lda >= m, ldb >= n, both strides multiples of 4, act in -1..1), else one of the values
+ * below.  GMP_WGRAD_ROUTE_LIBRARY: no kernel applies and gmp_edge_outer_sum_ex_f32 returns
+ * GMP_ERR_UNSUPPORTED (the caller runs the library GEMM); every valid shape outside the
+ * kernels' buckets gets it, at K = 0 too. */
+enum {
+  GMP_WGRAD_ROUTE_ZERO = 1,       /* K = 0: C and colsum_A zero-filled */
+  GMP_WGRAD_ROUTE_X3 = 2,         /* three bf16 planes, K >= 262144 */
+  GMP_WGRAD_ROUTE_QUAD = 3,       /* node-level 64 x 64 quadrants, 0 < K < 262144 */
+  GMP_WGRAD_ROUTE_SQUARE_F32 = 4, /* f32-MFMA square kernel, d in {32, 64, 128} */
+  GMP_WGRAD_ROUTE_RECT_F32 = 5,   /* f32-MFMA rectangular buckets, m <= 256 */
+  GMP_WGRAD_ROUTE_LIBRARY = 6     /* none: the caller's library GEMM */
+};
+int gmp_edge_outer_sum_ex_route(int64_t K, int64_t m, int64_t n, int64_t lda, int64_t ldb,
+                                int act);
 int gmp_edge_outer_sum_ex_f32(int64_t K, int64_t m, int64_t n, const float* A, int64_t lda,
                               const float* B, int64_t ldb, int act, const float* w, const float* b,
                               float* C, int64_t ldc, float* colsum_A, void* workspace,

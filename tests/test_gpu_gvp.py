@@ -668,3 +668,131 @@ def test_gvp_model_c3_uses_fused_ff():
     finally:
         g.GvpFFFn.apply = orig
     assert len(calls) == C3["num_layers"]
+
+
+@pytest.mark.parametrize("n", [0, 262_143, 262_144])
+def test_gvp_ff_fused_at_weight_sum_thresholds(n):
+    """K17 forward + backward where its four weight sums (576 x 192, 192 x 576, 192 x 64,
+    192 x 128 over the nodes) change route: no nodes (zero fill / library GEMM), the last
+    node-level size (quadrant kernel) and the first split-plane size (192 x 64 only; the other
+    three go to the library GEMM).  Reference: the oracle's two GVPs in fp64 on the device;
+    bounds as test_gvp_ff_fused_vs_oracle (1e-5 of scale for outputs, 1e-4 of scale for
+    gradients, plus twice the error of the oracle's fp32 chain on the device).  n = 0: outputs
+    with no rows and exact zeros for all twelve parameter gradients."""
+    import gmp_amd.gvp as g
+    ref = _ff_pair(77)
+    ref64 = copy.deepcopy(ref).double().to(DEV)
+    ref32 = copy.deepcopy(ref).to(DEV)
+    lay = torch.nn.Sequential(g.GVP((128, 16), (512, 32), activations=(RELU, None),
+                                    vector_gate=True),
+                              g.GVP((512, 32), (128, 16), activations=(None, None),
+                                    vector_gate=True))
+    lay.load_state_dict(ref.state_dict())
+    lay = lay.to(DEV)
+    gen = torch.Generator(device=DEV).manual_seed(n + 3)
+    s = torch.randn(n, 128, generator=gen, device=DEV)
+    v = torch.randn(n, 16, 3, generator=gen, device=DEV)
+    gs = torch.randn(n, 128, generator=gen, device=DEV)
+    gv = torch.randn(n, 16, 3, generator=gen, device=DEV)
+    if n:
+        v[3] = 0.0           # every |vh| of both GVPs at the clamp
+        v[5, :8] = 0.0
+        # Of n x 512 first-GVP pre-activations some thousand lie within fp32 rounding of the ReLU
+        # kink, where a correct fp32 evaluation may take the other branch than fp64 (as in
+        # test_gvp_ff_fused_matches_chain_and_is_deterministic); each such row moves the
+        # gradients by more than the bounds and would hide a lost row behind the fp32 chain's
+        # allowance.  Rows with a pre-activation within 1e-4 of zero (fp32 rounding there:
+        # ~1e-6) get new scalars until none is left, so the bounds below are about arithmetic.
+        g1 = ref64[0]
+        with torch.no_grad():
+            vn = ogvp.norm_no_nan(g1.wh(v.double().transpose(-1, -2)), axis=-2)
+        for _ in range(8):
+            with torch.no_grad():
+                pre = g1.ws(torch.cat([s.double(), vn], -1))
+            near = (pre.abs() < 1e-4).any(1)
+            if not near.any():
+                break
+            s[near] = torch.randn(int(near.sum()), 128, generator=gen, device=DEV)
+        assert not near.any()
+
+    def run(f, dt):
+        si, vi = s.to(dt).clone().requires_grad_(True), v.to(dt).clone().requires_grad_(True)
+        so, vo = f((si, vi))
+        ((so * gs.to(dt)).sum() + (vo * gv.to(dt)).sum()).backward()
+        return so.detach(), vo.detach(), si.grad, vi.grad
+
+    assert g._ff_fusable(lay, (s, v))
+    got = run(lambda x: g.gvp_ff(lay, x), torch.float32)
+    torch.cuda.synchronize()
+    want, w32 = run(ref64, torch.float64), run(ref32, torch.float32)
+    named = [(k, p) for k, p in lay.named_parameters() if p.numel()]
+    assert len(named) == 12 and all(p.grad is not None for _, p in named)
+    if n == 0:
+        assert got[0].shape == (0, 128) and got[1].shape == (0, 16, 3)
+        assert got[2].shape == (0, 128) and got[3].shape == (0, 16, 3)
+        for k, p in named:
+            assert torch.count_nonzero(p.grad).item() == 0, k
+        return
+    for i, nm in enumerate(("s", "v")):
+        err = (got[i].double() - want[i]).abs().max().item()
+        e32 = (w32[i].double() - want[i]).abs().max().item()
+        assert err <= 1e-5 * max(1.0, want[i].abs().max().item()) + 2 * e32, (nm, err, e32)
+    pairs = [("ds", got[2], want[2], w32[2]), ("dv", got[3], want[3], w32[3])]
+    pairs += [(k, p.grad, q.grad, r.grad) for (k, p), q, r in
+              zip(named, [q for q in ref64.parameters() if q.numel()],
+                  [r for r in ref32.parameters() if r.numel()])]
+    for nm, a, b, b32 in pairs:
+        err = (a.double() - b).abs().max().item()
+        e32 = (b32.double() - b).abs().max().item()
+        sc = b.abs().max().item()
+        print(f"n={n} {nm}: err {err:.3e} fp32 chain {e32:.3e} scale {sc:.3e}")
+        assert err <= 1e-4 * sc + 2 * e32 + 1e-7, f"{nm}: {err:.3e} (fp32 chain {e32:.3e}, " \
+                                                  f"scale {sc:.3e})"
+
+
+def test_gvp_conv_layer_empty_node_mask(monkeypatch):
+    """GVPConvLayer forward + backward with a node_mask that selects nothing: the feed-forward
+    sees no rows (K17's weight sums at K = 0).  With GVP_FF_FUSED on and off the outputs and
+    every gradient are identical, and they are the CPU oracle's for the same mask: the inputs
+    returned unchanged, the output gradient passed through, zeros for every parameter."""
+    import gmp_amd.gvp as g
+    from gmp_amd.graph import radius_graph
+    torch.manual_seed(8)
+    gr = radius_graph(num_nodes=200, target_edges=2000, r=2.0, seed=6, tol=0.2, shuffle=True)
+    ref = ogvp.GVPConvLayer((128, 16), (32, 1), activations=(RELU, None), vector_gate=True).eval()
+    n, e = gr.num_nodes, gr.num_edges
+    s, v = torch.randn(n, 128), torch.randn(n, 16, 3)
+    es, ev = torch.randn(e, 32), torch.randn(e, 1, 3)
+    gs, gv = torch.randn(n, 128), torch.randn(n, 16, 3)
+    mask = torch.zeros(n, dtype=torch.bool)
+
+    def run(layer, dev):
+        layer.zero_grad(set_to_none=True)
+        leaves = [t.clone().to(dev).requires_grad_(True) for t in (s, v, es, ev)]
+        # the layer writes the selected rows into its input in place: not into a leaf
+        so, vo = layer((leaves[0].clone(), leaves[1].clone()), gr.edge_index.to(dev),
+                       (leaves[2], leaves[3]), node_mask=mask.to(dev))
+        ((so * gs.to(dev)).sum() + (vo * gv.to(dev)).sum()).backward()
+        if dev != "cpu":
+            torch.cuda.synchronize()
+        out = {"so": so.detach(), "vo": vo.detach()}
+        out.update({f"d{i}": t.grad for i, t in enumerate(leaves)})
+        out.update({k: p.grad for k, p in layer.named_parameters() if p.numel()})
+        return {k: (None if t is None else t.detach().cpu().clone()) for k, t in out.items()}
+
+    want = run(ref, "cpu")
+    assert torch.equal(want["so"], s) and torch.equal(want["d0"], gs)
+    lay = g.GVPConvLayer((128, 16), (32, 1), activations=(RELU, None), vector_gate=True)
+    lay.load_state_dict(ref.state_dict(), strict=True)
+    lay = lay.to(DEV).eval()
+    res = {}
+    for fused in (True, False):
+        monkeypatch.setattr(g, "GVP_FF_FUSED", fused)
+        res[fused] = run(lay, DEV)
+    assert set(res[True]) == set(res[False]) == set(want)
+    for k, w in want.items():
+        a, b = res[True][k], res[False][k]
+        assert (a is None) == (b is None) == (w is None), k
+        if w is not None:
+            assert torch.equal(a, b), k
+            assert torch.equal(a, w), k
