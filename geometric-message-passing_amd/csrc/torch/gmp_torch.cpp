@@ -557,6 +557,14 @@ Tensor xyz_norm_bwd(const Tensor& vh, const Tensor& gout) {
 }
 
 // ------------------------------------------------------------------ K1 featurisation
+// workspace of the shifted featurisation entry points (empty without a shift)
+Tensor shift_workspace(const optional<Tensor>& shift, const Tensor& like, int64_t E) {
+  if (!(shift.has_value() && shift->defined() && E > 0)) return Tensor();
+  return at::empty({(int64_t)gmp_featurize_shift_workspace_size(E)},
+                   like.options().dtype(at::kByte));
+}
+void* wsp(const Tensor& ws) { return ws.defined() ? ws.data_ptr() : nullptr; }
+size_t wsn(const Tensor& ws) { return ws.defined() ? (size_t)ws.numel() : 0; }
 int64_t edge_checks(const Tensor& pos, const Tensor& edge_index) {
   f32(pos, "pos");
   i64(edge_index, "edge_index");
@@ -567,24 +575,28 @@ int64_t edge_checks(const Tensor& pos, const Tensor& edge_index) {
 
 std::tuple<Tensor, Tensor> edge_featurize(const Tensor& pos, const Tensor& edge_index,
                                           at::ArrayRef<double> bessel_w, double prefactor,
-                                          double r_max, double p, int64_t lmax) {
+                                          double r_max, double p, int64_t lmax,
+                                          const optional<Tensor>& shift) {
   OpGuard g(pos, "edge_featurize");
   const int64_t E = edge_checks(pos, edge_index), nb = (int64_t)bessel_w.size();
   TORCH_CHECK(0 <= lmax && lmax <= 5, "gmp.edge_featurize: lmax in 0..5");
   std::vector<float> w(bessel_w.begin(), bessel_w.end());
   Tensor sh = at::empty({E, (lmax + 1) * (lmax + 1)}, pos.options());
   Tensor rad = at::empty({E, nb}, pos.options());
-  check_rc(gmp_edge_featurize_lmax_f32(fp(pos), ip(edge_index), E, (int)lmax, (int)nb, w.data(),
-                                       (float)prefactor, (float)r_max, (float)p, nullptr, nullptr,
-                                       fp(sh), fp(rad), cur_stream()),
-           "gmp_edge_featurize_lmax_f32");
+  opt_f32(shift, {E, 3}, "shift");
+  Tensor ws = shift_workspace(shift, pos, E);
+  check_rc(gmp_edge_featurize_lmax_ex_f32(fp(pos), ip(edge_index), E, (int)lmax, (int)nb,
+                                          w.data(), (float)prefactor, (float)r_max, (float)p,
+                                          cfp(shift), wsp(ws), wsn(ws), nullptr, nullptr, fp(sh), fp(rad),
+                                          cur_stream()),
+           "gmp_edge_featurize_lmax_ex_f32");
   return {sh, rad};
 }
 
 Tensor edge_featurize_bwd(const Tensor& pos, const Tensor& edge_index,
                           at::ArrayRef<double> bessel_w, double prefactor, double r_max, double p,
                           const optional<Tensor>& g_sh, const optional<Tensor>& g_rad,
-                          int64_t lmax) {
+                          int64_t lmax, const optional<Tensor>& shift) {
   OpGuard g(pos, "edge_featurize_bwd");
   const int64_t E = edge_checks(pos, edge_index), nb = (int64_t)bessel_w.size();
   TORCH_CHECK(0 <= lmax && lmax <= 5, "gmp.edge_featurize_bwd: lmax in 0..5");
@@ -592,10 +604,13 @@ Tensor edge_featurize_bwd(const Tensor& pos, const Tensor& edge_index,
   opt_f32(g_rad, {E, nb}, "g_radial");
   std::vector<float> w(bessel_w.begin(), bessel_w.end());
   Tensor gv = at::empty({E, 3}, pos.options());
-  check_rc(gmp_edge_featurize_lmax_bwd_f32(fp(pos), ip(edge_index), E, (int)lmax, (int)nb,
-                                           w.data(), (float)prefactor, (float)r_max, (float)p,
-                                           cfp(g_sh), cfp(g_rad), fp(gv), cur_stream()),
-           "gmp_edge_featurize_lmax_bwd_f32");
+  opt_f32(shift, {E, 3}, "shift");
+  Tensor ws = shift_workspace(shift, pos, E);
+  check_rc(gmp_edge_featurize_lmax_bwd_ex_f32(fp(pos), ip(edge_index), E, (int)lmax, (int)nb,
+                                              w.data(), (float)prefactor, (float)r_max, (float)p,
+                                              cfp(shift), wsp(ws), wsn(ws), cfp(g_sh), cfp(g_rad), fp(gv),
+                                              cur_stream()),
+           "gmp_edge_featurize_lmax_bwd_ex_f32");
   return gv;
 }
 
@@ -632,23 +647,26 @@ Tensor edge_featurize_gvp_bwd(const Tensor& pos, const Tensor& edge_index,
 
 std::tuple<Tensor, Tensor, Tensor> schnet_featurize(const Tensor& pos, const Tensor& edge_index,
                                                     const Tensor& offsets, double coeff,
-                                                    double cutoff) {
+                                                    double cutoff, const optional<Tensor>& shift) {
   OpGuard g(pos, "schnet_featurize");
   const int64_t E = edge_checks(pos, edge_index);
   f32(offsets, "offsets");
   const int64_t G = offsets.numel();
   Tensor d = at::empty({E}, pos.options()), rbf = at::empty({E, G}, pos.options()),
          cut = at::empty({E}, pos.options());
-  check_rc(gmp_schnet_featurize_f32(fp(pos), ip(edge_index), E, (int)G, fp(offsets),
-                                    (float)coeff, (float)cutoff, fp(d), fp(rbf), fp(cut),
-                                    cur_stream()),
-           "gmp_schnet_featurize_f32");
+  opt_f32(shift, {E, 3}, "shift");
+  Tensor ws = shift_workspace(shift, pos, E);
+  check_rc(gmp_schnet_featurize_ex_f32(fp(pos), ip(edge_index), E, (int)G, fp(offsets),
+                                       (float)coeff, (float)cutoff, cfp(shift), wsp(ws), wsn(ws), fp(d), fp(rbf),
+                                       fp(cut), cur_stream()),
+           "gmp_schnet_featurize_ex_f32");
   return {d, rbf, cut};
 }
 
 Tensor schnet_featurize_bwd(const Tensor& pos, const Tensor& edge_index, const Tensor& offsets,
                             double coeff, double cutoff, const optional<Tensor>& g_dist,
-                            const optional<Tensor>& g_rbf, const optional<Tensor>& g_cut) {
+                            const optional<Tensor>& g_rbf, const optional<Tensor>& g_cut,
+                            const optional<Tensor>& shift) {
   OpGuard g(pos, "schnet_featurize_bwd");
   const int64_t E = edge_checks(pos, edge_index);
   f32(offsets, "offsets");
@@ -657,10 +675,12 @@ Tensor schnet_featurize_bwd(const Tensor& pos, const Tensor& edge_index, const T
   opt_f32(g_rbf, {E, G}, "g_rbf");
   opt_f32(g_cut, {E}, "g_cut");
   Tensor gv = at::empty({E, 3}, pos.options());
-  check_rc(gmp_schnet_featurize_bwd_f32(fp(pos), ip(edge_index), E, (int)G, fp(offsets),
-                                        (float)coeff, (float)cutoff, cfp(g_dist), cfp(g_rbf),
-                                        cfp(g_cut), fp(gv), cur_stream()),
-           "gmp_schnet_featurize_bwd_f32");
+  opt_f32(shift, {E, 3}, "shift");
+  Tensor ws = shift_workspace(shift, pos, E);
+  check_rc(gmp_schnet_featurize_bwd_ex_f32(fp(pos), ip(edge_index), E, (int)G, fp(offsets),
+                                           (float)coeff, (float)cutoff, cfp(shift), wsp(ws), wsn(ws), cfp(g_dist),
+                                           cfp(g_rbf), cfp(g_cut), fp(gv), cur_stream()),
+           "gmp_schnet_featurize_bwd_ex_f32");
   return gv;
 }
 
@@ -670,7 +690,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> schnet_featurize_bwd2(
     const Tensor& pos, const Tensor& edge_index, const Tensor& offsets, double coeff,
     double cutoff, const optional<Tensor>& g_dist, const optional<Tensor>& g_rbf,
     const optional<Tensor>& g_cut, const Tensor& a_vec, bool want_dist, bool want_rbf,
-    bool want_cut, bool want_vec) {
+    bool want_cut, bool want_vec, const optional<Tensor>& shift) {
   OpGuard g(pos, "schnet_featurize_bwd2");
   const int64_t E = edge_checks(pos, edge_index);
   f32(offsets, "offsets");
@@ -683,12 +703,41 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> schnet_featurize_bwd2(
   auto o = pos.options();
   Tensor gd = at::empty({want_dist ? E : 0}, o), gr = at::empty({want_rbf ? E : 0, G}, o),
          gc = at::empty({want_cut ? E : 0}, o), hv = at::empty({want_vec ? E : 0, 3}, o);
-  check_rc(gmp_schnet_featurize_bwd2_f32(fp(pos), pos.size(0), ip(edge_index), E, (int)G,
-                                         fp(offsets), (float)coeff, (float)cutoff, cfp(g_dist),
-                                         cfp(g_rbf), cfp(g_cut), fp(a_vec), fp(gd), fp(gr), fp(gc),
-                                         fp(hv), cur_stream()),
-           "gmp_schnet_featurize_bwd2_f32");
+  opt_f32(shift, {E, 3}, "shift");
+  Tensor ws = shift_workspace(shift, pos, E);
+  check_rc(gmp_schnet_featurize_bwd2_ex_f32(fp(pos), pos.size(0), ip(edge_index), E, (int)G,
+                                            fp(offsets), (float)coeff, (float)cutoff, cfp(shift), wsp(ws), wsn(ws),
+                                            cfp(g_dist), cfp(g_rbf), cfp(g_cut), fp(a_vec),
+                                            fp(gd), fp(gr), fp(gc), fp(hv), cur_stream()),
+           "gmp_schnet_featurize_bwd2_ex_f32");
   return {gd, gr, gc, hv};
+}
+
+// t (E, 3) of the periodic contract (include/gmp.h K9p) from edge_shift_idx (E, 3) int32,
+// cell (B, 3, 3) and each edge's graph (E) int64
+Tensor edge_shift_vectors(const Tensor& edge_shift_idx, const Tensor& cell,
+                          const optional<Tensor>& edge_graph) {
+  OpGuard g(cell, "edge_shift_vectors");
+  i32(edge_shift_idx, "edge_shift_idx");
+  f32(cell, "cell");
+  TORCH_CHECK(edge_shift_idx.dim() == 2 && edge_shift_idx.size(1) == 3,
+              "gmp: edge_shift_idx must be (E, 3)");
+  TORCH_CHECK(cell.dim() == 3 && cell.size(0) >= 1 && cell.size(1) == 3 && cell.size(2) == 3,
+              "gmp: cell must be (B, 3, 3)");
+  const int64_t E = edge_shift_idx.size(0);
+  if (edge_graph.has_value() && edge_graph->defined()) {
+    i64(*edge_graph, "edge_graph");
+    numel(*edge_graph, E, "edge_graph");
+  } else {
+    TORCH_CHECK(cell.size(0) == 1, "gmp.edge_shift_vectors: edge_graph is needed with B > 1");
+  }
+  Tensor out = at::empty({E, 3}, cell.options());
+  check_rc(gmp_edge_shift_vectors_f32(
+               E ? edge_shift_idx.data_ptr<int32_t>() : nullptr, fp(cell),
+               edge_graph.has_value() && edge_graph->defined() ? ip(*edge_graph) : nullptr, E,
+               cell.size(0), fp(out), cur_stream()),
+           "gmp_edge_shift_vectors_f32");
+  return out;
 }
 
 // ------------------------------------------------------------------ K16 Gate / BatchNorm
@@ -1729,13 +1778,13 @@ Tensor xyz_norm_fwd(const Tensor& vh) { return at::empty({vh.size(0), vh.size(2)
 Tensor xyz_norm_bwd(const Tensor& vh, const Tensor&) { return at::empty_like(vh); }
 std::tuple<Tensor, Tensor> edge_featurize(const Tensor& pos, const Tensor& ei,
                                           at::ArrayRef<double> w, double, double, double,
-                                          int64_t lmax) {
+                                          int64_t lmax, const optional<Tensor>&) {
   return {at::empty({ei.size(1), (lmax + 1) * (lmax + 1)}, pos.options()),
           at::empty({ei.size(1), (int64_t)w.size()}, pos.options())};
 }
 Tensor edge_featurize_bwd(const Tensor& pos, const Tensor& ei, at::ArrayRef<double>, double,
                           double, double, const optional<Tensor>&, const optional<Tensor>&,
-                          int64_t) {
+                          int64_t, const optional<Tensor>&) {
   return at::empty({ei.size(1), 3}, pos.options());
 }
 std::tuple<Tensor, Tensor> edge_featurize_gvp(const Tensor& pos, const Tensor& ei,
@@ -1748,20 +1797,24 @@ Tensor edge_featurize_gvp_bwd(const Tensor& pos, const Tensor& ei, at::ArrayRef<
   return at::empty({ei.size(1), 3}, pos.options());
 }
 std::tuple<Tensor, Tensor, Tensor> schnet_featurize(const Tensor& pos, const Tensor& ei,
-                                                    const Tensor& offsets, double, double) {
+                                                    const Tensor& offsets, double, double,
+                                                    const optional<Tensor>&) {
   const int64_t E = ei.size(1);
   return {at::empty({E}, pos.options()), at::empty({E, offsets.numel()}, pos.options()),
           at::empty({E}, pos.options())};
 }
 Tensor schnet_featurize_bwd(const Tensor& pos, const Tensor& ei, const Tensor&, double, double,
                             const optional<Tensor>&, const optional<Tensor>&,
-                            const optional<Tensor>&) {
+                            const optional<Tensor>&, const optional<Tensor>&) {
   return at::empty({ei.size(1), 3}, pos.options());
+}
+Tensor edge_shift_vectors(const Tensor& sidx, const Tensor& cell, const optional<Tensor>&) {
+  return at::empty({sidx.size(0), 3}, cell.options());
 }
 std::tuple<Tensor, Tensor, Tensor, Tensor> schnet_featurize_bwd2(
     const Tensor& pos, const Tensor& ei, const Tensor& offsets, double, double,
     const optional<Tensor>&, const optional<Tensor>&, const optional<Tensor>&, const Tensor&,
-    bool want_dist, bool want_rbf, bool want_cut, bool want_vec) {
+    bool want_dist, bool want_rbf, bool want_cut, bool want_vec, const optional<Tensor>&) {
   const int64_t E = ei.size(1);
   auto o = pos.options();
   return {at::empty({want_dist ? E : 0}, o), at::empty({want_rbf ? E : 0, offsets.numel()}, o),
@@ -1971,22 +2024,25 @@ TORCH_LIBRARY(gmp, m) {
   m.def("xyz_norm_fwd(Tensor vh) -> Tensor");
   m.def("xyz_norm_bwd(Tensor vh, Tensor grad_out) -> Tensor");
   m.def("edge_featurize(Tensor pos, Tensor edge_index, float[] bessel_weights, float prefactor, "
-        "float r_max, float p, int lmax=2) -> (Tensor sh, Tensor radial)");
+        "float r_max, float p, int lmax=2, Tensor? shift=None) -> (Tensor sh, Tensor radial)");
   m.def("edge_featurize_bwd(Tensor pos, Tensor edge_index, float[] bessel_weights, "
-        "float prefactor, float r_max, float p, Tensor? g_sh, Tensor? g_radial, int lmax=2) "
-        "-> Tensor");
+        "float prefactor, float r_max, float p, Tensor? g_sh, Tensor? g_radial, int lmax=2, "
+        "Tensor? shift=None) -> Tensor");
   m.def("edge_featurize_gvp(Tensor pos, Tensor edge_index, float[] bessel_weights, "
         "float prefactor, float r_max, float p) -> (Tensor radial, Tensor unit)");
   m.def("edge_featurize_gvp_bwd(Tensor pos, Tensor edge_index, float[] bessel_weights, "
         "float prefactor, float r_max, float p, Tensor? g_radial, Tensor? g_unit) -> Tensor");
   m.def("schnet_featurize(Tensor pos, Tensor edge_index, Tensor offsets, float coeff, "
-        "float cutoff) -> (Tensor dist, Tensor rbf, Tensor cut)");
+        "float cutoff, Tensor? shift=None) -> (Tensor dist, Tensor rbf, Tensor cut)");
   m.def("schnet_featurize_bwd(Tensor pos, Tensor edge_index, Tensor offsets, float coeff, "
-        "float cutoff, Tensor? g_dist, Tensor? g_rbf, Tensor? g_cut) -> Tensor");
+        "float cutoff, Tensor? g_dist, Tensor? g_rbf, Tensor? g_cut, Tensor? shift=None) -> "
+        "Tensor");
+  m.def("edge_shift_vectors(Tensor edge_shift_idx, Tensor cell, Tensor? edge_graph=None) -> "
+        "Tensor");
   m.def("schnet_featurize_bwd2(Tensor pos, Tensor edge_index, Tensor offsets, float coeff, "
         "float cutoff, Tensor? g_dist, Tensor? g_rbf, Tensor? g_cut, Tensor a_vec, "
-        "bool want_dist=True, bool want_rbf=True, bool want_cut=True, bool want_vec=True) -> "
-        "(Tensor gg_dist, Tensor gg_rbf, Tensor gg_cut, Tensor h_vec)");
+        "bool want_dist=True, bool want_rbf=True, bool want_cut=True, bool want_vec=True, "
+        "Tensor? shift=None) -> (Tensor gg_dist, Tensor gg_rbf, Tensor gg_cut, Tensor h_vec)");
   m.def("gate_fwd(Tensor x, Tensor out_map, float c_act, float c_gate) -> Tensor");
   m.def("gate_bwd(Tensor x, Tensor grad_y, Tensor in_map, float c_act, float c_gate) -> Tensor");
   m.def("irreps_bn_fwd(Tensor x, Tensor col_chan, Tensor chan_col, Tensor chan_info, "
@@ -2083,6 +2139,7 @@ TORCH_LIBRARY(gmp, m) {
   m.impl("schnet_featurize", ns schnet_featurize);                        \
   m.impl("schnet_featurize_bwd", ns schnet_featurize_bwd);                \
   m.impl("schnet_featurize_bwd2", ns schnet_featurize_bwd2);              \
+  m.impl("edge_shift_vectors", ns edge_shift_vectors);                    \
   m.impl("gate_fwd", ns gate_fwd);                                        \
   m.impl("gate_bwd", ns gate_bwd);                                        \
   m.impl("irreps_bn_fwd", ns irreps_bn_fwd);                              \

@@ -9,7 +9,8 @@ from .scatter import (scatter, scatter_sum, scatter_add, scatter_mean, scatter_m
                       scatter_min, global_add_pool, global_mean_pool)
 from .message_passing import MessagePassing  # noqa: F401
 from .egnn import EGNNLayer, EGNNModel  # noqa: F401
-from .graph import Batch, collate, radius_graph, create_kchains  # noqa: F401
+from .graph import (Batch, collate, radius_graph, create_kchains,  # noqa: F401
+                    radius_graph_gpu, radius_graph_pbc_gpu, pbc_grid_plan)
 from .equivariant import (TensorProductConvLayer, MACEModel, TFNModel,  # noqa: F401
                           RadialEmbeddingBlock, EquivariantProductBasisBlock,
                           SymmetricContraction, first_node_pooling)
@@ -24,4 +25,4 @@ __all__ = ["scatter", "scatter_sum", "scatter_add", "scatter_mean", "scatter_max
            "MACEModel", "TFNModel", "RadialEmbeddingBlock", "EquivariantProductBasisBlock",
            "SymmetricContraction", "first_node_pooling", "GVP", "GVPConv", "GVPConvLayer",
            "GVPGNNModel", "SchNetModel", "CFConv", "InteractionBlock", "second_order",
-           "energy_and_forces"]
+           "energy_and_forces", "radius_graph_gpu", "radius_graph_pbc_gpu", "pbc_grid_plan"]

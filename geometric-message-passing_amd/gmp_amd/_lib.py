@@ -224,6 +224,25 @@ SIGNATURES = {
     "gmp_ssp_bwd2_f32": (c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "gmp_schnet_featurize_bwd2_f32": (c_int, [c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_f32, c_f32]
                                       + [c_vp] * 9),
+    # the featurisation entry points with a per-edge shift (periodic images)
+    "gmp_featurize_shift_workspace_size": (c_size, [c_i64]),
+    "gmp_edge_featurize_lmax_ex_f32": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_f32,
+                                               c_f32, c_f32, c_vp, c_vp, c_size] + [c_vp] * 5),
+    "gmp_edge_featurize_lmax_bwd_ex_f32": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_f32,
+                                                   c_f32, c_f32, c_vp, c_vp, c_size]
+                                           + [c_vp] * 4),
+    "gmp_schnet_featurize_ex_f32": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_f32, c_f32, c_vp,
+                                            c_vp, c_size] + [c_vp] * 4),
+    "gmp_schnet_featurize_bwd_ex_f32": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_f32, c_f32,
+                                                c_vp, c_vp, c_size] + [c_vp] * 5),
+    "gmp_schnet_featurize_bwd2_ex_f32": (c_int, [c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_f32,
+                                                 c_f32, c_vp, c_vp, c_size] + [c_vp] * 9),
+    # K9p: periodic radius graph
+    "gmp_radius_pbc_sort_capacity": (c_int, []),
+    "gmp_radius_pbc_bins_f32": (c_int, [c_vp, c_vp, c_i64, c_i64] + [c_vp] * 7),
+    "gmp_radius_pbc_count_f32": (c_int, [c_vp, c_vp, c_i64, c_i64, c_f32] + [c_vp] * 10),
+    "gmp_radius_pbc_fill_f32": (c_int, [c_vp, c_vp, c_i64, c_i64, c_f32] + [c_vp] * 12),
+    "gmp_edge_shift_vectors_f32": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp]),
 }
 
 # include/gmp.h GMP_ABI_VERSION (6: r06 — K17 gmp_gvp_ff_{fwd,bwd}_f32, K15b gmp_egnn_node_bwd_f32;

@@ -144,6 +144,10 @@ class EGNNModel(nn.Module):
                 and not ops.compiling() and not ops.egnn_exact_mode())
 
     def forward(self, batch):
+        if getattr(batch, "edge_shift_idx", None) is not None:
+            raise NotImplementedError(
+                "EGNNModel takes no periodic images (batch.edge_shift_idx): its edge geometry "
+                "is computed inside the fused kernels")
         h = ops.gather(self.emb_in.weight, batch.atoms)  # == emb_in(atoms); bwd = segmented sum
         pos = batch.pos
         if self._layers_fused(h, pos):

@@ -22,6 +22,7 @@ from torch.nn import functional as F
 
 from . import _lib, ops
 from . import o3
+from .graph import edge_shift
 from .ops import _f32c, _need_cuda, _timed
 from .scatter import global_add_pool, global_mean_pool, scatter
 
@@ -79,36 +80,42 @@ class RadialEmbeddingBlock(nn.Module):
 
 class EdgeFeaturizeFn(torch.autograd.Function):
     """K1: (pos, edge_index) -> (edge_sh (E, (lmax+1)^2), edge_feats (E,nb)) in one pass over the
-    edges (lmax <= 5: the models' max_ell; l = 4, 5 by e3nn's CG recursion)."""
+    edges (lmax <= 5: the models' max_ell; l = 4, 5 by e3nn's CG recursion).  shift (E, 3), if
+    given, is added to the edge vector (periodic images); its cotangent is g_vec."""
 
     @staticmethod
-    def forward(ctx, pos, edge_index, host_consts, graph, lmax=2):
+    def forward(ctx, pos, edge_index, host_consts, graph, lmax=2, shift=None):
         w, pref, r_max, p = host_consts
         pos = _f32c(pos)
         ei = edge_index.contiguous()
         _need_cuda(pos, ei)
+        sh_t = _f32c(shift) if shift is not None else None
         with _timed("edge_featurize"):
             sh, rad = _lib.torch_ops().edge_featurize(pos, ei, [float(v) for v in w], pref, r_max,
-                                                      p, lmax)
-        ctx.save_for_backward(pos, ei)
+                                                      p, lmax, sh_t)
+        ctx.save_for_backward(pos, ei, sh_t)
         ctx.host, ctx.graph, ctx.lmax = host_consts, graph, lmax
         return sh, rad
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g_sh, g_rad):
-        if not ctx.needs_input_grad[0]:
-            return None, None, None, None, None
-        pos, ei = ctx.saved_tensors
+        need_pos, need_shift = ctx.needs_input_grad[0], ops._needs(ctx, 5)
+        if not (need_pos or need_shift):
+            return None, None, None, None, None, None
+        pos, ei, sh_t = ctx.saved_tensors
         w, pref, r_max, p = ctx.host
         g_vec = _lib.torch_ops().edge_featurize_bwd(
             pos, ei, [float(v) for v in w], pref, r_max, p,
             _f32c(g_sh) if g_sh is not None else None,
-            _f32c(g_rad) if g_rad is not None else None, ctx.lmax)
-        g = ctx.graph  # vectors = pos[ei0] - pos[ei1]: + into receivers, - into senders
-        plus, _ = ops.segment_reduce(g_vec, g.recv_csr, "sum")
-        minus, _ = ops.segment_reduce(ops.gather_rows(g_vec, g.perm), g.src_csr, "sum")
-        return plus - minus, None, None, None, None
+            _f32c(g_rad) if g_rad is not None else None, ctx.lmax, sh_t)
+        dpos = None
+        if need_pos:
+            g = ctx.graph  # vectors = pos[ei0] - pos[ei1]: + into receivers, - into senders
+            plus, _ = ops.segment_reduce(g_vec, g.recv_csr, "sum")
+            minus, _ = ops.segment_reduce(ops.gather_rows(g_vec, g.perm), g.src_csr, "sum")
+            dpos = plus - minus
+        return dpos, None, None, None, None, g_vec if need_shift else None
 
 
 def spherical_harmonics_l2(vec, normalize=True):
@@ -1084,7 +1091,7 @@ class EquivariantProductBasisBlock(nn.Module):
 def _edge_features(model, batch):
     graph = tp_graph(batch.edge_index, batch.pos.shape[0])
     return EdgeFeaturizeFn.apply(batch.pos, batch.edge_index, model.radial_embedding._host, graph,
-                                 model.max_ell)
+                                 model.max_ell, edge_shift(batch))
 
 
 class MACEModel(nn.Module):

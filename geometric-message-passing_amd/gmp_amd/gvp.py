@@ -792,6 +792,10 @@ class GVPGNNModel(nn.Module):
                                       nn.Linear(s_dim, out_dim))
 
     def forward(self, batch):
+        if getattr(batch, "edge_shift_idx", None) is not None:
+            raise NotImplementedError(
+                "GVPGNNModel takes no periodic images (batch.edge_shift_idx): its edge geometry "
+                "is computed inside the fused kernels")
         ei = batch.edge_index
         # K1: radial embedding of |vec| and nan_to_num(vec / |vec|) in one pass (gvpgnn.py:106-112)
         rad, unit = ops.GvpEdgeFeaturizeFn.apply(batch.pos, ei, self.radial_embedding._host)

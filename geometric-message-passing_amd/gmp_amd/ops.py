@@ -695,31 +695,41 @@ class GvpEdgeFeaturizeFn(torch.autograd.Function):
         return edge_vec_to_pos_grad(g_vec, ei, pos.shape[0]), None, None
 
 
+def _needs(ctx, k):
+    """needs_input_grad[k] of an optional trailing input (absent: False)."""
+    return len(ctx.needs_input_grad) > k and ctx.needs_input_grad[k]
+
+
 class SchNetFeaturizeFn(torch.autograd.Function):
     """SchNet edge features (schnet.py:66-68 over PyG SchNet.forward / GaussianSmearing /
     CFConv.forward) in one pass over the edges (gmp_schnet_featurize_f32): edge_weight (E),
-    Gaussians (E, G) and the CFConv cosine cutoff C (E)."""
+    Gaussians (E, G) and the CFConv cosine cutoff C (E).  shift (E, 3), if given, is added to the
+    edge vector (periodic images); its cotangent is g_vec."""
 
     @staticmethod
-    def forward(ctx, pos, edge_index, offsets, coeff, cutoff):
+    def forward(ctx, pos, edge_index, offsets, coeff, cutoff, shift=None):
         pos, ei, off = _f32c(pos), _i64c(edge_index), _f32c(offsets)
         _need_cuda(pos, ei, off)
+        sh = _f32c(shift) if shift is not None else None
         with _timed("edge_featurize"):
             d, rbf, cut = _lib.torch_ops().schnet_featurize(pos, ei, off, float(coeff),
-                                                            float(cutoff))
-        ctx.save_for_backward(pos, ei, off)
+                                                            float(cutoff), sh)
+        ctx.save_for_backward(pos, ei, off, sh)
         ctx.coeff, ctx.cutoff = float(coeff), float(cutoff)
         return d, rbf, cut
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g_d, g_rbf, g_cut):
-        if not ctx.needs_input_grad[0]:
-            return None, None, None, None, None
-        pos, ei, off = ctx.saved_tensors
+        need_pos, need_shift = ctx.needs_input_grad[0], _needs(ctx, 5)
+        if not (need_pos or need_shift):
+            return None, None, None, None, None, None
+        pos, ei, off, sh = ctx.saved_tensors
         opt = [_f32c(t) if t is not None else None for t in (g_d, g_rbf, g_cut)]
-        g_vec = _lib.torch_ops().schnet_featurize_bwd(pos, ei, off, ctx.coeff, ctx.cutoff, *opt)
-        return edge_vec_to_pos_grad(g_vec, ei, pos.shape[0]), None, None, None, None
+        g_vec = _lib.torch_ops().schnet_featurize_bwd(pos, ei, off, ctx.coeff, ctx.cutoff, *opt,
+                                                      sh)
+        return (edge_vec_to_pos_grad(g_vec, ei, pos.shape[0]) if need_pos else None, None, None,
+                None, None, g_vec if need_shift else None)
 
 
 # ----------------------------------------------------------------------------------- EGNN
@@ -1195,55 +1205,108 @@ class EdgePosDiffFn(torch.autograd.Function):
         return EdgeVecToPosFn.apply(g, ctx.ei, ctx.n), None
 
 
-class SchNetFeaturize2Fn(torch.autograd.Function):
-    """SchNetFeaturizeFn whose backward is recorded (SchNetFeaturizeBwdFn, EdgeVecToPosFn)."""
+class EdgeShiftVectorsFn(torch.autograd.Function):
+    """t (E, 3) = S_e . cell[graph_e] with the periodic contract's rounding
+    (gmp_edge_shift_vectors_f32); linear in cell, its transpose is EdgeShiftToCellFn."""
 
     @staticmethod
-    def forward(ctx, pos, edge_index, offsets, coeff, cutoff):
+    def forward(ctx, cell, edge_shift_idx, edge_graph):
+        ctx.sidx, ctx.graph, ctx.B = edge_shift_idx, edge_graph, cell.shape[0]
+        return _lib.torch_ops().edge_shift_vectors(edge_shift_idx, _f32c(cell), edge_graph)
+
+    @staticmethod
+    def backward(ctx, g):
+        return EdgeShiftToCellFn.apply(g, ctx.sidx, ctx.graph, ctx.B), None, None
+
+
+class EdgeShiftToCellFn(torch.autograd.Function):
+    """d cell (B, 3, 3) = sum over the edges e of graph b of S_e (x) g_e: the deterministic
+    segmented sum over the cached CSR of edge_graph; its transpose is EdgeShiftVectorsFn."""
+
+    @staticmethod
+    def forward(ctx, g, edge_shift_idx, edge_graph, B):
+        ctx.sidx, ctx.graph = edge_shift_idx, edge_graph
+        outer = (edge_shift_idx.to(torch.float32).unsqueeze(2) * _f32c(g).unsqueeze(1))
+        out, _ = segment_reduce(outer.reshape(-1, 9), get_csr(edge_graph, B), "sum")
+        return out.view(B, 3, 3)
+
+    @staticmethod
+    def backward(ctx, a):
+        return EdgeShiftVectorsFn.apply(a, ctx.sidx, ctx.graph), None, None, None
+
+
+def edge_shift_vectors(edge_shift_idx, cell, edge_graph=None):
+    """Cartesian shift t (E, 3) of each edge's periodic image (the contract of include/gmp.h,
+    K9p) from edge_shift_idx (E, 3) int32, cell (B, 3, 3) and edge_graph (E): the graph of each
+    edge, batch[edge_index[1]]; None for a single graph.  Differentiable in cell, to any order."""
+    _need_cuda(cell, edge_shift_idx)
+    sidx = edge_shift_idx.to(torch.int32).contiguous()
+    if edge_graph is None:
+        if cell.shape[0] != 1:
+            raise ValueError("edge_graph is needed when cell holds more than one graph")
+        edge_graph = torch.zeros(sidx.shape[0], dtype=torch.int64, device=sidx.device)
+    return EdgeShiftVectorsFn.apply(cell, sidx, _i64c(edge_graph))
+
+
+class SchNetFeaturize2Fn(torch.autograd.Function):
+    """SchNetFeaturizeFn whose backward is recorded (SchNetFeaturizeBwdFn, EdgeVecToPosFn).
+    The cotangent of shift (E, 3), if given, is that g_vec."""
+
+    @staticmethod
+    def forward(ctx, pos, edge_index, offsets, coeff, cutoff, shift=None):
         ei, off = _i64c(edge_index), _f32c(offsets)
         _need_cuda(pos, ei, off)
         with _timed("edge_featurize"):
-            d, rbf, cut = _lib.torch_ops().schnet_featurize(_f32c(pos), ei, off, float(coeff),
-                                                            float(cutoff))
-        ctx.save_for_backward(pos, ei, off)
+            d, rbf, cut = _lib.torch_ops().schnet_featurize(
+                _f32c(pos), ei, off, float(coeff), float(cutoff),
+                _f32c(shift) if shift is not None else None)
+        ctx.save_for_backward(pos, ei, off, shift)
         ctx.coeff, ctx.cutoff = float(coeff), float(cutoff)
         ctx.set_materialize_grads(False)
         return d, rbf, cut
 
     @staticmethod
     def backward(ctx, g_d, g_rbf, g_cut):
-        if not ctx.needs_input_grad[0] or (g_d is None and g_rbf is None and g_cut is None):
-            return None, None, None, None, None
-        pos, ei, off = ctx.saved_tensors
-        g_vec = SchNetFeaturizeBwdFn.apply(pos, ei, off, ctx.coeff, ctx.cutoff, g_d, g_rbf, g_cut)
-        return EdgeVecToPosFn.apply(g_vec, ei, pos.shape[0]), None, None, None, None
+        need_pos, need_shift = ctx.needs_input_grad[0], _needs(ctx, 5)
+        if not (need_pos or need_shift) or (g_d is None and g_rbf is None and g_cut is None):
+            return None, None, None, None, None, None
+        pos, ei, off, shift = ctx.saved_tensors
+        g_vec = SchNetFeaturizeBwdFn.apply(pos, ei, off, ctx.coeff, ctx.cutoff, g_d, g_rbf, g_cut,
+                                           shift)
+        return (EdgeVecToPosFn.apply(g_vec, ei, pos.shape[0]) if need_pos else None, None, None,
+                None, None, g_vec if need_shift else None)
 
 
 class SchNetFeaturizeBwdFn(torch.autograd.Function):
     """g_vec (E, 3) from pos and the cotangents g_d / g_rbf / g_cut (each may be None)
     (gmp_schnet_featurize_bwd_f32); backward by gmp_schnet_featurize_bwd2_f32, whose h_vec goes
-    to pos through the segmented sums.  The second backward is once-differentiable."""
+    to pos through the segmented sums and, as it is, to shift (E, 3) if given.  The second
+    backward is once-differentiable."""
 
     @staticmethod
-    def forward(ctx, pos, ei, off, coeff, cutoff, g_d, g_rbf, g_cut):
-        ctx.save_for_backward(pos, ei, off, g_d, g_rbf, g_cut)
+    def forward(ctx, pos, ei, off, coeff, cutoff, g_d, g_rbf, g_cut, shift=None):
+        ctx.save_for_backward(pos, ei, off, g_d, g_rbf, g_cut, shift)
         ctx.coeff, ctx.cutoff = coeff, cutoff
         opt = [_f32c(t) if t is not None else None for t in (g_d, g_rbf, g_cut)]
-        return _lib.torch_ops().schnet_featurize_bwd(_f32c(pos), ei, off, coeff, cutoff, *opt)
+        return _lib.torch_ops().schnet_featurize_bwd(
+            _f32c(pos), ei, off, coeff, cutoff, *opt, _f32c(shift) if shift is not None else None)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, a_vec):
-        pos, ei, off, *opt = ctx.saved_tensors
+        pos, ei, off, *opt, shift = ctx.saved_tensors
         g_d, g_rbf, g_cut = [_f32c(t) if t is not None else None for t in opt]
         need = ctx.needs_input_grad
+        need_shift = _needs(ctx, 8)
         want = (g_d is not None and need[5], g_rbf is not None and need[6],
-                g_cut is not None and need[7], need[0])
+                g_cut is not None and need[7], need[0] or need_shift)
         gg_d, gg_rbf, gg_cut, h_vec = _lib.torch_ops().schnet_featurize_bwd2(
-            _f32c(pos), ei, off, ctx.coeff, ctx.cutoff, g_d, g_rbf, g_cut, _f32c(a_vec), *want)
-        dpos = edge_vec_to_pos_grad(h_vec, ei, pos.shape[0]) if want[3] else None
+            _f32c(pos), ei, off, ctx.coeff, ctx.cutoff, g_d, g_rbf, g_cut, _f32c(a_vec), *want,
+            _f32c(shift) if shift is not None else None)
+        dpos = edge_vec_to_pos_grad(h_vec, ei, pos.shape[0]) if need[0] else None
         return (dpos, None, None, None, None, gg_d if want[0] else None,
-                gg_rbf if want[1] else None, gg_cut if want[2] else None)
+                gg_rbf if want[1] else None, gg_cut if want[2] else None,
+                h_vec if need_shift else None)
 
 
 class SegmentReduce2Fn(torch.autograd.Function):

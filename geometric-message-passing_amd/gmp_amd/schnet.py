@@ -17,6 +17,7 @@ from torch import nn
 from torch.nn import functional as F
 
 from . import ops
+from .graph import edge_shift
 from .message_passing import MessagePassing
 from .scatter import global_add_pool, global_mean_pool
 
@@ -137,7 +138,7 @@ class SchNetModel(nn.Module):
         ds = self.distance_expansion
         feat = ops.SchNetFeaturize2Fn if ops.second_order_enabled() else ops.SchNetFeaturizeFn
         edge_weight, edge_attr, C = feat.apply(
-            batch.pos, batch.edge_index, ds.offset, ds.coeff, self.cutoff)
+            batch.pos, batch.edge_index, ds.offset, ds.coeff, self.cutoff, edge_shift(batch))
         if not all(isinstance(i.conv, CFConv) and i.conv.cutoff == self.cutoff
                    for i in self.interactions):
             C = None

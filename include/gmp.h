@@ -380,6 +380,26 @@ int gmp_edge_featurize_lmax_bwd_f32(const float* pos, const int64_t* edge_index,
                                     const float* bessel_weights, float prefactor, float r_max,
                                     float p_cutoff, const float* g_sh, const float* g_radial,
                                     float* g_vec, void* stream);
+/* The same with a per-edge Cartesian shift (E,3) added to vec (periodic images, K9p:
+ * vec = (pos[ei0] - pos[ei1]) + shift).  shift == NULL is the entry point above, bit for bit
+ * (and takes no workspace).  With a shift, a first pass writes the shifted vectors and a
+ * redirected edge list into `workspace` (DEVICE, 16-byte aligned,
+ * gmp_featurize_shift_workspace_size(n_edges) bytes) and the same kernel runs on them, so
+ * shift = zeros gives bitwise the NULL result.  The backward formulas are unchanged and the
+ * cotangent of shift is g_vec itself.  The SchNet entry points below follow the same rule. */
+size_t gmp_featurize_shift_workspace_size(int64_t n_edges);
+int gmp_edge_featurize_lmax_ex_f32(const float* pos, const int64_t* edge_index, int64_t n_edges,
+                                   int lmax, int num_bessel, const float* bessel_weights,
+                                   float prefactor, float r_max, float p_cutoff,
+                                   const float* shift, void* workspace, size_t workspace_bytes,
+                                   float* vec_out, float* len_out, float* sh_out,
+                                   float* radial_out, void* stream);
+int gmp_edge_featurize_lmax_bwd_ex_f32(const float* pos, const int64_t* edge_index,
+                                       int64_t n_edges, int lmax, int num_bessel,
+                                       const float* bessel_weights, float prefactor, float r_max,
+                                       float p_cutoff, const float* shift, void* workspace,
+                                       size_t workspace_bytes, const float* g_sh,
+                                       const float* g_radial, float* g_vec, void* stream);
 /* GVP-GNN edge features (models/gvpgnn.py:106-112): len (E), radial (E,nb) as above and the unit
  * vectors nan_to_num(vec / len) (E,3; zero rows for zero-length edges).  Backward from g_radial /
  * g_unit (either may be NULL) to g_vec. */
@@ -417,6 +437,28 @@ int gmp_schnet_featurize_bwd2_f32(const float* pos, int64_t n_nodes, const int64
                                   const float* g_rbf, const float* g_cut, const float* a_vec,
                                   float* gg_dist, float* gg_rbf, float* gg_cut, float* h_vec,
                                   void* stream);
+/* The three SchNet entry points with a per-edge Cartesian shift (E,3) added to the edge vector
+ * (periodic images, K9p: dist = |(pos[row] - pos[col]) + shift|).  shift == NULL is the entry
+ * point above, bit for bit; workspace as for gmp_edge_featurize_lmax_ex_f32.  The cotangent of
+ * shift is g_vec (h_vec in the second backward). */
+int gmp_schnet_featurize_ex_f32(const float* pos, const int64_t* edge_index, int64_t n_edges,
+                                int num_gaussians, const float* offsets, float coeff,
+                                float cutoff, const float* shift, void* workspace,
+                                size_t workspace_bytes, float* dist_out, float* rbf_out,
+                                float* cut_out, void* stream);
+int gmp_schnet_featurize_bwd_ex_f32(const float* pos, const int64_t* edge_index, int64_t n_edges,
+                                    int num_gaussians, const float* offsets, float coeff,
+                                    float cutoff, const float* shift, void* workspace,
+                                    size_t workspace_bytes, const float* g_dist,
+                                    const float* g_rbf, const float* g_cut, float* g_vec,
+                                    void* stream);
+int gmp_schnet_featurize_bwd2_ex_f32(const float* pos, int64_t n_nodes, const int64_t* edge_index,
+                                     int64_t n_edges, int num_gaussians, const float* offsets,
+                                     float coeff, float cutoff, const float* shift,
+                                     void* workspace, size_t workspace_bytes, const float* g_dist,
+                                     const float* g_rbf, const float* g_cut, const float* a_vec,
+                                     float* gg_dist, float* gg_rbf, float* gg_cut, float* h_vec,
+                                     void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * K16 irreps epilogues of the TP convolution (models/layers/tfn_layer.py:89-92), row-major
@@ -738,6 +780,59 @@ int gmp_radius_fill_f32(const float* pos, const int64_t* batch, int64_t n_nodes,
                         const int* dims3, const int64_t* cell, const int64_t* cell_rowptr,
                         const int64_t* cell_perm, const int64_t* offsets, int64_t* src_out,
                         void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * K9p radius graph under periodic boundary conditions.  THE CONTRACT (stated here only):
+ *   pos (N,3) f32; cell (B,3,3) f32, rows = lattice vectors, one cell per graph; pbc: three
+ *   booleans shared by all graphs; batch (N) or NULL (one graph); r > 0.
+ * An edge (j -> i, S) exists for every S in Z^3 with S_k = 0 on each non-periodic axis, i and j
+ * in the same graph b, (j, S) != (i, 0) and d2 < r2, where, in fp32 with every operation
+ * rounded to nearest and nothing contracted (K9's rule),
+ *   t  = ((S0*c[b,0,:] + S1*c[b,1,:]) + S2*c[b,2,:])
+ *   dx = (p_i - p_j) - t                       (per component)
+ *   d2 = (dx*dx + dy*dy) + dz*dz,   r2 = r*r.
+ * Self-image edges (i == j, S != 0) and edges between coincident distinct atoms are edges.  The
+ * result is defined on pos as given: atoms need not lie inside the cell.  There is no neighbour
+ * cap.  Output: edge_index (2,E) int64 [sources; targets] and edge_shift_idx (E,3) int32, both
+ * sorted by (i, j, S0, S1, S2); |S_k| <= 127.  The featurised vector of an edge is
+ * (pos[src] - pos[dst]) + t, the exact negative of dx.
+ *
+ * Per-graph plan (DEVICE arrays, computed by the caller in fp64 from one copy of cell; the
+ * margin argument is in gmp_radius_pbc.hip):
+ *   graph_i (B,8) int32: nb[3] bins per axis, m[3] reach in bins, periodic-axis bit mask, 0;
+ *   graph_f (B,24) f32: inv[9] (frac_k = sum_d p_d inv[3d+k]), org[3] and scale[3] (bin
+ *     coordinate of a non-periodic axis = (frac - org) * scale; periodic: (frac - floor(frac))
+ *     * scale with scale = nb), cell[9];
+ *   graph_base (B) int64: first bin of each graph in the bin table.
+ * bins:  bin id and packed wraps floor(frac) per node -> the caller buckets nodes with
+ *        gmp_csr_build over the bin table (bin_rowptr, bin_perm);
+ * count: edges per target;  fill: sources and shift indices of target i at offsets[i] ..
+ *        offsets[i+1], sorted (targets with more than gmp_radius_pbc_sort_capacity() edges are
+ *        sorted in global memory instead of LDS).
+ * *err_flag (DEVICE, zeroed by the caller) is set to 1 for a batch entry outside [0, B), a
+ * wrap or shift beyond 127, or counts that do not match the fill.
+ * gmp_edge_shift_vectors_f32: t (E,3) of the contract from edge_shift_idx, cell and each edge's
+ * graph (NULL: graph 0); an edge whose graph is outside [0, B) gets zeros.
+ * ------------------------------------------------------------------------------------------ */
+int gmp_radius_pbc_sort_capacity(void);
+int gmp_radius_pbc_bins_f32(const float* pos, const int64_t* batch, int64_t n_nodes,
+                            int64_t n_graphs, const int* graph_i, const float* graph_f,
+                            const int64_t* graph_base, int64_t* bin_out, int* wrap_out,
+                            int32_t* err_flag, void* stream);
+int gmp_radius_pbc_count_f32(const float* pos, const int64_t* batch, int64_t n_nodes,
+                             int64_t n_graphs, float r, const int* graph_i, const float* graph_f,
+                             const int64_t* graph_base, const int64_t* bin, const int* wrap,
+                             const int64_t* bin_rowptr, const int64_t* bin_perm, int64_t* counts,
+                             int32_t* err_flag, void* stream);
+int gmp_radius_pbc_fill_f32(const float* pos, const int64_t* batch, int64_t n_nodes,
+                            int64_t n_graphs, float r, const int* graph_i, const float* graph_f,
+                            const int64_t* graph_base, const int64_t* bin, const int* wrap,
+                            const int64_t* bin_rowptr, const int64_t* bin_perm,
+                            const int64_t* offsets, int64_t* src_out, int* shift_idx_out,
+                            int32_t* err_flag, void* stream);
+int gmp_edge_shift_vectors_f32(const int* edge_shift_idx, const float* cell,
+                               const int64_t* edge_graph, int64_t n_edges, int64_t n_graphs,
+                               float* shift_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * K10 batch collation (PyG Batch.from_data_list as the reference's loaders
