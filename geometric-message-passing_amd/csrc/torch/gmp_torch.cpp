@@ -1685,6 +1685,212 @@ std::vector<Tensor> gvp_msg0_bwd_agg(const Tensor& send, const Tensor& recv, con
   return {dspre, spre, dgate, vn, vh, dvpre, dvh, des, dev, dPb, dQb, sgr, svr};
 }
 
+// ------------------------------------------------------------------ K18 / K19: SphereNet
+int64_t pad8(int64_t v) { return (v + 7) / 8 * 8; }
+
+void sph_tables(const Tensor& zeros, const Tensor& norm, int64_t* n, int64_t* k) {
+  f32(zeros, "zeros");
+  f32(norm, "norm");
+  TORCH_CHECK(zeros.dim() == 2 && zeros.size(0) >= 1 && zeros.size(1) >= 1,
+              "gmp: zeros is (num_spherical, num_radial)");
+  shape(norm, zeros.sizes(), "norm");
+  *n = zeros.size(0);
+  *k = zeros.size(1);
+}
+
+std::tuple<Tensor, Tensor> sph_edge_basis_fwd(const Tensor& dist, const Tensor& freq,
+                                              const Tensor& zeros, const Tensor& norm,
+                                              double cutoff, int64_t envelope_exponent) {
+  OpGuard g(dist, "sph_edge_basis_fwd");
+  f32(dist, "dist");
+  f32(freq, "freq");
+  int64_t n, k;
+  sph_tables(zeros, norm, &n, &k);
+  TORCH_CHECK(dist.dim() == 1, "gmp.sph_edge_basis_fwd: dist (E)");
+  numel(freq, k, "freq");
+  const int64_t E = dist.numel();
+  Tensor rbf = at::empty({E, k}, dist.options()), jb = at::empty({E, n * k}, dist.options());
+  check_rc(gmp_sph_edge_basis_fwd_f32(fp(dist), E, (float)cutoff, (int)envelope_exponent,
+                                      fp(freq), (int)k, fp(zeros), fp(norm), (int)n, fp(rbf),
+                                      fp(jb), cur_stream()),
+           "gmp_sph_edge_basis_fwd_f32");
+  return {rbf, jb};
+}
+
+std::tuple<Tensor, Tensor> sph_edge_basis_bwd(const Tensor& dist, const Tensor& freq,
+                                              const Tensor& zeros, const Tensor& norm,
+                                              double cutoff, int64_t envelope_exponent,
+                                              const optional<Tensor>& grad_rbf,
+                                              const optional<Tensor>& grad_jb) {
+  OpGuard g(dist, "sph_edge_basis_bwd");
+  f32(dist, "dist");
+  f32(freq, "freq");
+  int64_t n, k;
+  sph_tables(zeros, norm, &n, &k);
+  TORCH_CHECK(dist.dim() == 1, "gmp.sph_edge_basis_bwd: dist (E)");
+  numel(freq, k, "freq");
+  const int64_t E = dist.numel();
+  opt_f32(grad_rbf, {E, k}, "grad_rbf");
+  opt_f32(grad_jb, {E, n * k}, "grad_jb");
+  Tensor gd = at::empty({E}, dist.options()), gf = at::empty({k}, dist.options());
+  Tensor part = at::empty({gmp_sph_edge_basis_bwd_partial_rows(E), k}, dist.options());
+  check_rc(gmp_sph_edge_basis_bwd_f32(fp(dist), E, (float)cutoff, (int)envelope_exponent,
+                                      fp(freq), (int)k, fp(zeros), fp(norm), (int)n,
+                                      cfp(grad_rbf), cfp(grad_jb), fp(gd), fp(gf), fp(part),
+                                      cur_stream()),
+           "gmp_sph_edge_basis_bwd_f32");
+  return {gd, gf};
+}
+
+// shared argument checks of the per-triplet K18 entry points; returns T
+int64_t sph_triplet_args(const Tensor& jb, const Tensor& angle, const Tensor& torsion,
+                         const Tensor& idx_kj, const Tensor& pref, int64_t n, int64_t k) {
+  f32(jb, "jb");
+  f32(angle, "angle");
+  f32(torsion, "torsion");
+  i64(idx_kj, "idx_kj");
+  f32(pref, "pref");
+  TORCH_CHECK(n >= 1 && k >= 1 && jb.dim() == 2 && jb.size(1) == n * k,
+              "gmp: jb (E, num_spherical * num_radial)");
+  numel(pref, n * n, "pref");
+  const int64_t T = angle.numel();
+  numel(torsion, T, "torsion");
+  numel(idx_kj, T, "idx_kj");
+  return T;
+}
+
+void sph_proj_weights(const Tensor& w1t, const Tensor& w2t, int64_t n, int64_t k, int64_t L,
+                      int64_t ba, int64_t bt) {
+  f32(w1t, "w_sbf1_t");
+  f32(w2t, "w_t1_t");
+  TORCH_CHECK(L >= 1 && ba >= 1 && bt >= 1, "gmp: n_layers, ba, bt >= 1");
+  shape(w1t, {n * k, pad8(L * ba)}, "w_sbf1_t");
+  shape(w2t, {n * n * k, pad8(L * bt)}, "w_t1_t");
+}
+
+std::tuple<Tensor, Tensor> sph_triplet_proj_fwd(const Tensor& jb, const Tensor& angle,
+                                                const Tensor& torsion, const Tensor& idx_kj,
+                                                const Tensor& pref, const Tensor& w1t,
+                                                const Tensor& w2t, int64_t n, int64_t k,
+                                                int64_t L, int64_t ba, int64_t bt) {
+  OpGuard g(jb, "sph_triplet_proj_fwd");
+  const int64_t T = sph_triplet_args(jb, angle, torsion, idx_kj, pref, n, k);
+  sph_proj_weights(w1t, w2t, n, k, L, ba, bt);
+  Tensor S = at::empty({L, T, ba}, jb.options()), P = at::empty({L, T, bt}, jb.options());
+  check_rc(gmp_sph_triplet_proj_fwd_f32(T, jb.size(0), (int)n, (int)k, fp(jb), fp(angle),
+                                        fp(torsion), ip(idx_kj), fp(pref), fp(w1t), (int)L,
+                                        (int)ba, fp(w2t), (int)bt, fp(S), fp(P), cur_stream()),
+           "gmp_sph_triplet_proj_fwd_f32");
+  return {S, P};
+}
+
+std::tuple<Tensor, Tensor> sph_triplet_emb(const Tensor& jb, const Tensor& angle,
+                                           const Tensor& torsion, const Tensor& idx_kj,
+                                           const Tensor& pref, int64_t n, int64_t k) {
+  OpGuard g(jb, "sph_triplet_emb");
+  const int64_t T = sph_triplet_args(jb, angle, torsion, idx_kj, pref, n, k);
+  Tensor a = at::empty({T, n * k}, jb.options()), t = at::empty({T, n * n * k}, jb.options());
+  check_rc(gmp_sph_triplet_emb_f32(T, jb.size(0), (int)n, (int)k, fp(jb), fp(angle), fp(torsion),
+                                   ip(idx_kj), fp(pref), fp(a), fp(t), cur_stream()),
+           "gmp_sph_triplet_emb_f32");
+  return {a, t};
+}
+
+// (grad w_sbf1_t, grad w_t1_t, grad_jb_rows (T, n k), grad_angle (T), grad_torsion (T)); the
+// last three are empty without want_geometry
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> sph_triplet_proj_bwd(
+    const Tensor& jb, const Tensor& angle, const Tensor& torsion, const Tensor& idx_kj,
+    const Tensor& pref, const Tensor& w1t, const Tensor& w2t, int64_t n, int64_t k, int64_t L,
+    int64_t ba, int64_t bt, const Tensor& gS, const Tensor& gP, bool want_geometry) {
+  OpGuard g(jb, "sph_triplet_proj_bwd");
+  const int64_t T = sph_triplet_args(jb, angle, torsion, idx_kj, pref, n, k);
+  sph_proj_weights(w1t, w2t, n, k, L, ba, bt);
+  f32(gS, "grad_S");
+  f32(gP, "grad_P");
+  shape(gS, {L, T, ba}, "grad_S");
+  shape(gP, {L, T, bt}, "grad_P");
+  auto o = jb.options();
+  const int64_t w1 = w1t.numel(), w2 = w2t.numel();
+  Tensor gw = at::empty({w1 + w2}, o);
+  Tensor part = at::empty({gmp_sph_triplet_proj_bwd_partial_rows(T), w1 + w2}, o);
+  const int64_t Tg = want_geometry ? T : 0;
+  Tensor gjb = at::empty({Tg, n * k}, o), ga = at::empty({Tg}, o), gt = at::empty({Tg}, o);
+  check_rc(gmp_sph_triplet_proj_bwd_f32(
+               T, jb.size(0), (int)n, (int)k, fp(jb), fp(angle), fp(torsion), ip(idx_kj), fp(pref),
+               fp(w1t), (int)L, (int)ba, fp(w2t), (int)bt, fp(gS), fp(gP), fp(gw), fp(part),
+               fp(gjb), fp(ga), fp(gt), cur_stream()),
+           "gmp_sph_triplet_proj_bwd_f32");
+  return {gw.narrow(0, 0, w1).view(w1t.sizes()), gw.narrow(0, w1, w2).view(w2t.sizes()), gjb, ga,
+          gt};
+}
+
+// shared checks of K19
+void interact_args(const Tensor& S, const Tensor& P, const Tensor& wa, const Tensor& wt) {
+  f32(S, "S");
+  f32(P, "P");
+  f32(wa, "w_sbf2");
+  f32(wt, "w_t2");
+  TORCH_CHECK(S.dim() == 2 && P.dim() == 2 && S.size(0) == P.size(0) && wa.dim() == 2 &&
+                  wt.dim() == 2 && wa.size(0) == wt.size(0) && wa.size(0) >= 1 &&
+                  wa.size(1) == S.size(1) && wt.size(1) == P.size(1) && S.size(1) >= 1 &&
+                  P.size(1) >= 1,
+              "gmp: S (T, ba), P (T, bt), w_sbf2 (I, ba), w_t2 (I, bt)");
+}
+
+Tensor triplet_interact_fwd(const Tensor& src, const Tensor& S, const Tensor& P, const Tensor& wa,
+                            const Tensor& wt, const Tensor& gidx, const optional<Tensor>& perm,
+                            const Tensor& rowptr) {
+  OpGuard g(src, "triplet_interact_fwd");
+  f32(src, "src");
+  interact_args(S, P, wa, wt);
+  i64(gidx, "gather_idx");
+  i64(rowptr, "rowptr");
+  const int64_t T = S.size(0), I = wa.size(0);
+  TORCH_CHECK(src.dim() == 2 && src.size(1) == I, "gmp.triplet_interact_fwd: src (n_src, I)");
+  numel(gidx, T, "gather_idx");
+  TORCH_CHECK(rowptr.numel() >= 1, "gmp.triplet_interact_fwd: rowptr (n_seg + 1)");
+  const bool hp = perm.has_value() && perm->defined();
+  if (hp) {
+    i64(*perm, "perm");
+    numel(*perm, T, "perm");
+  }
+  const int64_t n_seg = rowptr.numel() - 1;
+  Tensor out = at::empty({n_seg, I}, src.options());
+  check_rc(gmp_triplet_interact_fwd_f32(n_seg, src.size(0), T, I, (int)S.size(1), (int)P.size(1),
+                                        fp(src), fp(S), fp(P), fp(wa), fp(wt), ip(gidx),
+                                        hp ? ip(*perm) : nullptr, ip(rowptr), fp(out),
+                                        cur_stream()),
+           "gmp_triplet_interact_fwd_f32");
+  return out;
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor> triplet_interact_bwd(
+    const Tensor& gm, const Tensor& xd, const Tensor& S, const Tensor& P, const Tensor& wa,
+    const Tensor& wt, const Tensor& idx_kj, const Tensor& offs) {
+  OpGuard g(gm, "triplet_interact_bwd");
+  f32(gm, "grad_m");
+  f32(xd, "xd");
+  interact_args(S, P, wa, wt);
+  i64(idx_kj, "idx_kj");
+  i64(offs, "offsets");
+  const int64_t T = S.size(0), I = wa.size(0), ba = S.size(1), bt = P.size(1);
+  TORCH_CHECK(xd.dim() == 2 && xd.size(1) == I, "gmp.triplet_interact_bwd: xd (E, I)");
+  const int64_t E = xd.size(0);
+  shape(gm, {E, I}, "grad_m");
+  numel(idx_kj, T, "idx_kj");
+  numel(offs, E + 1, "offsets");
+  TORCH_CHECK(ba <= 16 && bt <= 16, "gmp.triplet_interact_bwd: basis_emb sizes <= 16");
+  auto o = gm.options();
+  Tensor gS = at::empty({T, ba}, o), gP = at::empty({T, bt}, o);
+  Tensor gw = at::empty({I * (ba + bt)}, o);
+  Tensor part = at::empty({gmp_triplet_interact_bwd_partial_rows(E), I * (ba + bt)}, o);
+  check_rc(gmp_triplet_interact_bwd_f32(E, T, I, (int)ba, (int)bt, fp(gm), fp(xd), fp(S), fp(P),
+                                        fp(wa), fp(wt), ip(idx_kj), ip(offs), fp(gS), fp(gP),
+                                        fp(gw), fp(part), cur_stream()),
+           "gmp_triplet_interact_bwd_f32");
+  return {gS, gP, gw.narrow(0, 0, I * ba).view({I, ba}), gw.narrow(0, I * ba, I * bt).view({I, bt})};
+}
+
 // ------------------------------------------------------------------ Meta (shape) kernels
 namespace meta {
 std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> csr_build(const Tensor& index, int64_t n_seg,
@@ -1981,6 +2187,47 @@ std::vector<Tensor> gvp_msg0_bwd_agg(const Tensor& send, const Tensor& recv, con
   out.push_back(at::empty({n_nodes, 48}, o));
   return out;
 }
+std::tuple<Tensor, Tensor> sph_edge_basis_fwd(const Tensor& dist, const Tensor&,
+                                              const Tensor& zeros, const Tensor&, double, int64_t) {
+  return {at::empty({dist.numel(), zeros.size(1)}, dist.options()),
+          at::empty({dist.numel(), zeros.numel()}, dist.options())};
+}
+std::tuple<Tensor, Tensor> sph_edge_basis_bwd(const Tensor& dist, const Tensor& freq, const Tensor&,
+                                              const Tensor&, double, int64_t,
+                                              const optional<Tensor>&, const optional<Tensor>&) {
+  return {at::empty_like(dist), at::empty_like(freq)};
+}
+std::tuple<Tensor, Tensor> sph_triplet_proj_fwd(const Tensor& jb, const Tensor& angle,
+                                                const Tensor&, const Tensor&, const Tensor&,
+                                                const Tensor&, const Tensor&, int64_t, int64_t,
+                                                int64_t L, int64_t ba, int64_t bt) {
+  return {at::empty({L, angle.numel(), ba}, jb.options()),
+          at::empty({L, angle.numel(), bt}, jb.options())};
+}
+std::tuple<Tensor, Tensor> sph_triplet_emb(const Tensor& jb, const Tensor& angle, const Tensor&,
+                                           const Tensor&, const Tensor&, int64_t n, int64_t k) {
+  return {at::empty({angle.numel(), n * k}, jb.options()),
+          at::empty({angle.numel(), n * n * k}, jb.options())};
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> sph_triplet_proj_bwd(
+    const Tensor& jb, const Tensor& angle, const Tensor&, const Tensor&, const Tensor&,
+    const Tensor& w1t, const Tensor& w2t, int64_t n, int64_t k, int64_t, int64_t, int64_t,
+    const Tensor&, const Tensor&, bool want_geometry) {
+  const int64_t Tg = want_geometry ? angle.numel() : 0;
+  auto o = jb.options();
+  return {at::empty_like(w1t), at::empty_like(w2t), at::empty({Tg, n * k}, o), at::empty({Tg}, o),
+          at::empty({Tg}, o)};
+}
+Tensor triplet_interact_fwd(const Tensor& src, const Tensor&, const Tensor&, const Tensor& wa,
+                            const Tensor&, const Tensor&, const optional<Tensor>&,
+                            const Tensor& rowptr) {
+  return at::empty({rowptr.numel() - 1, wa.size(0)}, src.options());
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor> triplet_interact_bwd(
+    const Tensor&, const Tensor&, const Tensor& S, const Tensor& P, const Tensor& wa,
+    const Tensor& wt, const Tensor&, const Tensor&) {
+  return {at::empty_like(S), at::empty_like(P), at::empty_like(wa), at::empty_like(wt)};
+}
 }  // namespace meta
 
 }  // namespace
@@ -2106,6 +2353,25 @@ TORCH_LIBRARY(gmp, m) {
   m.def("gvp_msg0_bwd_agg(Tensor send, Tensor recv, Tensor P, Tensor Q, Tensor es, Tensor ev, "
         "Tensor[] W, Tensor ds, Tensor dv, Tensor? perm, Tensor rowptr, int n_nodes, "
         "bool want_factors=True) -> Tensor[]");
+  m.def("sph_edge_basis_fwd(Tensor dist, Tensor freq, Tensor zeros, Tensor norm, float cutoff, "
+        "int envelope_exponent) -> (Tensor rbf, Tensor jb)");
+  m.def("sph_edge_basis_bwd(Tensor dist, Tensor freq, Tensor zeros, Tensor norm, float cutoff, "
+        "int envelope_exponent, Tensor? grad_rbf, Tensor? grad_jb) -> "
+        "(Tensor grad_dist, Tensor grad_freq)");
+  m.def("sph_triplet_proj_fwd(Tensor jb, Tensor angle, Tensor torsion, Tensor idx_kj, Tensor pref, "
+        "Tensor w_sbf1_t, Tensor w_t1_t, int num_spherical, int num_radial, int n_layers, int ba, "
+        "int bt) -> (Tensor S, Tensor P)");
+  m.def("sph_triplet_emb(Tensor jb, Tensor angle, Tensor torsion, Tensor idx_kj, Tensor pref, "
+        "int num_spherical, int num_radial) -> (Tensor angle_emb, Tensor torsion_emb)");
+  m.def("sph_triplet_proj_bwd(Tensor jb, Tensor angle, Tensor torsion, Tensor idx_kj, Tensor pref, "
+        "Tensor w_sbf1_t, Tensor w_t1_t, int num_spherical, int num_radial, int n_layers, int ba, "
+        "int bt, Tensor grad_S, Tensor grad_P, bool want_geometry) -> (Tensor grad_w_sbf1_t, "
+        "Tensor grad_w_t1_t, Tensor grad_jb_rows, Tensor grad_angle, Tensor grad_torsion)");
+  m.def("triplet_interact_fwd(Tensor src, Tensor S, Tensor P, Tensor w_sbf2, Tensor w_t2, "
+        "Tensor gather_idx, Tensor? perm, Tensor rowptr) -> Tensor");
+  m.def("triplet_interact_bwd(Tensor grad_m, Tensor xd, Tensor S, Tensor P, Tensor w_sbf2, "
+        "Tensor w_t2, Tensor idx_kj, Tensor offsets) -> (Tensor grad_S, Tensor grad_P, "
+        "Tensor grad_w_sbf2, Tensor grad_w_t2)");
 }
 
 #define GMP_IMPL(m, ns)                                                    \
@@ -2169,7 +2435,14 @@ TORCH_LIBRARY(gmp, m) {
   m.impl("gvp_layer_fwd_agg", ns gvp_layer_fwd_agg);                      \
   m.impl("gvp_msg0_bwd_agg", ns gvp_msg0_bwd_agg);                        \
   m.impl("gvp_msg0_fwd", ns gvp_msg0_fwd);                                \
-  m.impl("gvp_msg0_bwd", ns gvp_msg0_bwd);
+  m.impl("gvp_msg0_bwd", ns gvp_msg0_bwd);                                \
+  m.impl("sph_edge_basis_fwd", ns sph_edge_basis_fwd);                    \
+  m.impl("sph_edge_basis_bwd", ns sph_edge_basis_bwd);                    \
+  m.impl("sph_triplet_proj_fwd", ns sph_triplet_proj_fwd);                \
+  m.impl("sph_triplet_emb", ns sph_triplet_emb);                          \
+  m.impl("sph_triplet_proj_bwd", ns sph_triplet_proj_bwd);                \
+  m.impl("triplet_interact_fwd", ns triplet_interact_fwd);                \
+  m.impl("triplet_interact_bwd", ns triplet_interact_bwd);
 
 TORCH_LIBRARY_IMPL(gmp, CUDA, m) { GMP_IMPL(m, ) }
 // CPU tensors reach the same implementations, whose device guard rejects them with the

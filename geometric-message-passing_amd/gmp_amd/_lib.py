@@ -243,6 +243,22 @@ SIGNATURES = {
     "gmp_radius_pbc_count_f32": (c_int, [c_vp, c_vp, c_i64, c_i64, c_f32] + [c_vp] * 10),
     "gmp_radius_pbc_fill_f32": (c_int, [c_vp, c_vp, c_i64, c_i64, c_f32] + [c_vp] * 12),
     "gmp_edge_shift_vectors_f32": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp]),
+    # K18 / K19: SphereNet's spherical basis and triplet interaction; additions only
+    "gmp_sph_edge_basis_fwd_f32": (c_int, [c_vp, c_i64, c_f32, c_int, c_vp, c_int, c_vp, c_vp,
+                                           c_int, c_vp, c_vp, c_vp]),
+    "gmp_sph_edge_basis_bwd_partial_rows": (c_i64, [c_i64]),
+    "gmp_sph_edge_basis_bwd_f32": (c_int, [c_vp, c_i64, c_f32, c_int, c_vp, c_int, c_vp, c_vp,
+                                           c_int] + [c_vp] * 6),
+    "gmp_sph_triplet_proj_fwd_f32": (c_int, [c_i64, c_i64, c_int, c_int] + [c_vp] * 6
+                                     + [c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp]),
+    "gmp_sph_triplet_emb_f32": (c_int, [c_i64, c_i64, c_int, c_int] + [c_vp] * 8),
+    "gmp_sph_triplet_proj_bwd_partial_rows": (c_i64, [c_i64]),
+    "gmp_sph_triplet_proj_bwd_f32": (c_int, [c_i64, c_i64, c_int, c_int] + [c_vp] * 6
+                                     + [c_int, c_int, c_vp, c_int] + [c_vp] * 8),
+    "gmp_triplet_interact_fwd_f32": (c_int, [c_i64, c_i64, c_i64, c_i64, c_int, c_int]
+                                     + [c_vp] * 10),
+    "gmp_triplet_interact_bwd_partial_rows": (c_i64, [c_i64]),
+    "gmp_triplet_interact_bwd_f32": (c_int, [c_i64, c_i64, c_i64, c_int, c_int] + [c_vp] * 13),
 }
 
 # include/gmp.h GMP_ABI_VERSION (6: r06 — K17 gmp_gvp_ff_{fwd,bwd}_f32, K15b gmp_egnn_node_bwd_f32;

@@ -1418,3 +1418,157 @@ class EdgeOuterFn(torch.autograd.Function):
         if ctx.needs_input_grad[1] and aW is not None:
             dx = g.mm(aW)
         return dg, dx
+
+
+# ----------------------------------------------------------------------------------- SphereNet
+def _pad8(v):
+    return (v + 7) // 8 * 8
+
+
+class SphEdgeBasisFn(torch.autograd.Function):
+    """(rbf (E, k), jb (E, n k)) of K18 gmp_sph_edge_basis_*: the radial basis
+    envelope(x) sin(freq x) and the normalised spherical Bessel values N_lq j_l(z_lq x),
+    x = dist / cutoff.  Gradients reach dist and freq."""
+
+    @staticmethod
+    def forward(ctx, dist, freq, zeros, norm, cutoff, envelope_exponent):
+        dist, freq = _f32c(dist), _f32c(freq)
+        _need_cuda(dist, freq, zeros, norm)
+        ctx.save_for_backward(dist, freq, zeros, norm)
+        ctx.cutoff, ctx.p = float(cutoff), int(envelope_exponent)
+        return _lib.torch_ops().sph_edge_basis_fwd(dist, freq, zeros, norm, ctx.cutoff, ctx.p)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_rbf, g_jb):
+        dist, freq, zeros, norm = ctx.saved_tensors
+        g_rbf = _f32c(g_rbf) if g_rbf is not None else None
+        g_jb = _f32c(g_jb) if g_jb is not None else None
+        gd, gf = _lib.torch_ops().sph_edge_basis_bwd(dist, freq, zeros, norm, ctx.cutoff, ctx.p,
+                                                     g_rbf, g_jb)
+        return gd, gf, None, None, None, None
+
+
+def sph_feature_major(weights, width):
+    """The first projections of all layers, [(b, F)] * L, as one feature-major (F, pad8(L b))
+    matrix with column layer * b + j (the layout K18 reads)."""
+    L, b = len(weights), weights[0].shape[0]
+    w = torch.stack([_f32c(x) for x in weights]).reshape(L * b, width).t()
+    out = w.new_zeros((width, _pad8(L * b)))
+    out[:, :L * b] = w
+    return out
+
+
+class SphTripletProjFn(torch.autograd.Function):
+    """K18 gmp_sph_triplet_proj_*: S[l] = W_sbf1[l] angle_emb and P[l] = W_t1[l] torsion_emb for
+    every layer l at once, the embeddings formed on chip from jb[idx_kj], angle and torsion.
+    Returns (S[0], .., S[L-1], P[0], .., P[L-1]).  Gradients: the 2L weights and, where asked
+    for, jb (summed per edge over the CSR of idx_kj), angle and torsion."""
+
+    @staticmethod
+    def forward(ctx, jb, angle, torsion, idx_kj, pref, n, k, L, *weights):
+        jb, angle, torsion = _f32c(jb), _f32c(angle), _f32c(torsion)
+        idx_kj = _i64c(idx_kj)
+        _need_cuda(jb, angle, torsion, idx_kj, pref, *weights)
+        ba, bt = weights[0].shape[0], weights[L].shape[0]
+        w1t = sph_feature_major(weights[:L], n * k)
+        w2t = sph_feature_major(weights[L:], n * n * k)
+        S, P = _lib.torch_ops().sph_triplet_proj_fwd(jb, angle, torsion, idx_kj, pref, w1t, w2t,
+                                                     n, k, L, ba, bt)
+        ctx.save_for_backward(jb, angle, torsion, idx_kj, pref, w1t, w2t)
+        ctx.dims = (n, k, L, ba, bt)
+        return tuple(S.unbind(0)) + tuple(P.unbind(0))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        jb, angle, torsion, idx_kj, pref, w1t, w2t = ctx.saved_tensors
+        n, k, L, ba, bt = ctx.dims
+        T = angle.numel()
+
+        def stacked(gs, b):
+            out = jb.new_zeros((L, T, b))
+            for l, g in enumerate(gs):
+                if g is not None:
+                    out[l] = g
+            return out
+
+        gS, gP = stacked(grads[:L], ba), stacked(grads[L:], bt)
+        geom = any(ctx.needs_input_grad[:3])
+        gw1, gw2, gjb_rows, ga, gt = _lib.torch_ops().sph_triplet_proj_bwd(
+            jb, angle, torsion, idx_kj, pref, w1t, w2t, n, k, L, ba, bt, gS, gP, geom)
+        gjb = None
+        if geom and T == 0:
+            gjb = torch.zeros_like(jb)
+        elif geom:
+            gjb, _ = segment_reduce(gjb_rows, get_csr(idx_kj, jb.shape[0]), "sum")
+        else:
+            ga = gt = None
+        gw = [gw1[:, l * ba:(l + 1) * ba].t().contiguous() for l in range(L)]
+        gw += [gw2[:, l * bt:(l + 1) * bt].t().contiguous() for l in range(L)]
+        return (gjb, ga, gt, None, None, None, None, None) + tuple(gw)
+
+
+def sph_triplet_embeddings(jb, angle, torsion, idx_kj, pref, n, k):
+    """The materialised angle_emb (T, n k) and torsion_emb (T, n^2 k) of K18 (tests and small T;
+    the model never forms them)."""
+    _need_cuda(jb, angle, torsion, idx_kj, pref)
+    return _lib.torch_ops().sph_triplet_emb(_f32c(jb), _f32c(angle), _f32c(torsion),
+                                            _i64c(idx_kj), pref, n, k)
+
+
+class TripletInteractFn(torch.autograd.Function):
+    """K19 gmp_triplet_interact_*: m[e] = sum over the triplets t of edge e (the contiguous
+    range [offsets[e], offsets[e+1]) that K11 emits) of xd[idx_kj[t]] * (W_sbf2 S_t) *
+    (W_t2 P_t).  Deterministic both ways; grad_xd runs the same kernel over the CSR of idx_kj."""
+
+    @staticmethod
+    def forward(ctx, xd, S, P, Wa, Wt, idx_kj, idx_ji, offsets):
+        xd, S, P, Wa, Wt = _f32c(xd), _f32c(S), _f32c(P), _f32c(Wa), _f32c(Wt)
+        idx_kj, idx_ji, offsets = _i64c(idx_kj), _i64c(idx_ji), _i64c(offsets)
+        _need_cuda(xd, S, P, Wa, Wt, idx_kj, idx_ji, offsets)
+        ctx.save_for_backward(xd, S, P, Wa, Wt, idx_kj, idx_ji, offsets)
+        return _lib.torch_ops().triplet_interact_fwd(xd, S, P, Wa, Wt, idx_kj, None, offsets)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gm):
+        xd, S, P, Wa, Wt, idx_kj, idx_ji, offsets = ctx.saved_tensors
+        gm = _f32c(gm)
+        tops = _lib.torch_ops()
+        gS, gP, gWa, gWt = tops.triplet_interact_bwd(gm, xd, S, P, Wa, Wt, idx_kj, offsets)
+        gxd = None
+        if ctx.needs_input_grad[0]:
+            if idx_kj.numel() == 0 or xd.shape[0] == 0:
+                gxd = torch.zeros_like(xd)
+            else:
+                csr = get_csr(idx_kj, xd.shape[0])
+                gxd = tops.triplet_interact_fwd(gm, S, P, Wa, Wt, idx_ji, csr.perm, csr.rowptr)
+        return gxd, gS, gP, gWa, gWt, None, None, None
+
+
+class FirstOrderOnlyFn(torch.autograd.Function):
+    """Identity whose gradient raises when it is differentiated again (create_graph=True)
+    instead of passing as a constant: K11's geometry backward records no graph, and the
+    SphereNet path has no second-order kernels."""
+
+    @staticmethod
+    def forward(ctx, x):
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        if torch.is_grad_enabled():  # create_graph=True: the result must not pass as a constant
+            g = _NoSecondOrderFn.apply(g.detach().requires_grad_(True))
+        return g
+
+
+class _NoSecondOrderFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, g):
+        return g.view_as(g)
+
+    @staticmethod
+    def backward(ctx, a):
+        raise RuntimeError("this path is once differentiable: its gradient (e.g. a force) cannot "
+                           "be differentiated again")

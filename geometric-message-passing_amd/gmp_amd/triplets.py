@@ -143,3 +143,18 @@ def dimenet_angles(pos, edge_index, num_nodes):
     dist, angle, _, idx_kj, idx_ji = _geom(pos, edge_index, num_nodes, 1)
     row, col = edge_index
     return (dist, angle, col, row, col[idx_ji], row[idx_ji], row[idx_kj], idx_kj, idx_ji)
+
+
+def xyz_to_dat_offsets(pos, edge_index, num_nodes):
+    """xyz_to_dat(..., use_torsion=True) plus the triplet row pointer: -> dist, angle, torsion,
+    i, j, idx_kj, idx_ji, offsets (E + 1), the triplets of edge e being the contiguous range
+    [offsets[e], offsets[e+1]) (idx_ji is non-decreasing)."""
+    dist, angle, torsion, i, j, idx_kj, idx_ji = xyz_to_dat(pos, edge_index, num_nodes, True)
+    return dist, angle, torsion, i, j, idx_kj, idx_ji, triplet_offsets(idx_ji, dist.numel())
+
+
+def triplet_offsets(idx_ji, num_edges):
+    """Row pointer (E + 1) over the non-decreasing idx_ji (cached per graph)."""
+    if num_edges == 0 or idx_ji.numel() == 0:
+        return torch.zeros(num_edges + 1, dtype=torch.int64, device=idx_ji.device)
+    return ops.get_csr(idx_ji, num_edges).rowptr

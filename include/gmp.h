@@ -1010,6 +1010,89 @@ int gmp_ssp_bwd_f32(const float* x, const float* grad_y, int64_t n, float* grad_
 int gmp_ssp_bwd2_f32(const float* x, const float* grad_y, const float* a, int64_t n, float* gg,
                      float* gx, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K18 SphereNet spherical basis (models/layers/spherenet_layer.py dist_emb / angle_emb /
+ * torsion_emb).  Additions only: the ABI version is unchanged.  n = num_spherical (<= 16),
+ * k = num_radial (<= 64).  Host tables: zeros (n k) the fp32 zeros z_lq of j_l, norm (n k)
+ * the normalisers N_lq, pref (n^2) the harmonic prefactors by flat index l^2 + p, p = 0 (m = 0),
+ * 1..l (cos, m = p), l+1..2l (sin, m = 2l + 1 - p), sqrt(2) of m != 0 included.
+ *
+ * Edge basis, x = dist / cutoff (dist > 0):
+ *   rbf (E, k)  = envelope(x) sin(freq_q x), envelope(x) = 1/x + a x^(p-1) + b x^p + c x^(p+1),
+ *                 p = envelope_exponent + 1, a = -(p+1)(p+2)/2, b = p(p+2), c = -p(p+1)/2;
+ *   jb (E, n k) = N_lq j_l(z_lq x), accurate for every x in (0, z_max]: a power series below
+ *                 x = l + 1, the upward recurrence above (never the closed form over x^l).
+ *   bwd: grad_dist (E) from grad_rbf / grad_jb (either may be NULL) and grad_freq (k), the
+ *        latter through freq_partials (gmp_sph_edge_basis_bwd_partial_rows(E), k) in a fixed
+ *        order (no atomics).
+ *
+ * Triplet projection for L layers at once: the angle features jb[idx_kj[t]][l, q] Y_l0(angle_t)
+ * (n k of them, index l k + q) and the torsion features jb[idx_kj[t]][b, q] Yflat[a n + b]
+ * (angle_t, torsion_t) (n^2 k, index (a n + b) k + q) never leave the chip:
+ *   S (L, T, ba) = W_sbf1[l] angle_emb_t,   P (L, T, bt) = W_t1[l] torsion_emb_t.
+ * The weights come feature-major: w_sbf1_t (n k, lda), w_t1_t (n^2 k, ldt), column o =
+ * layer * b + j, lda / ldt = L ba / L bt rounded up to a multiple of 8, padding zero.
+ *   bwd: grad_w (n k lda + n^2 k ldt) = [grad w_sbf1_t | grad w_t1_t] recomputing the features,
+ *        through partials (gmp_sph_triplet_proj_bwd_partial_rows(T) rows of that width), summed
+ *        in a fixed order.  If grad_jb_rows (T, n k), grad_angle (T), grad_torsion (T) are
+ *        given (all or none) the geometry gradients are written too; the caller sums
+ *        grad_jb_rows per edge over the CSR of idx_kj.
+ *   emb: the materialised angle_emb (T, n k) and torsion_emb (T, n^2 k) (tests, small T).
+ * An idx_kj outside [0, E) contributes a zero jb row.
+ * ------------------------------------------------------------------------------------------ */
+int gmp_sph_edge_basis_fwd_f32(const float* dist, int64_t n_edges, float cutoff,
+                               int envelope_exponent, const float* freq, int num_radial,
+                               const float* zeros, const float* norm, int num_spherical,
+                               float* rbf, float* jb, void* stream);
+int64_t gmp_sph_edge_basis_bwd_partial_rows(int64_t n_edges);
+int gmp_sph_edge_basis_bwd_f32(const float* dist, int64_t n_edges, float cutoff,
+                               int envelope_exponent, const float* freq, int num_radial,
+                               const float* zeros, const float* norm, int num_spherical,
+                               const float* grad_rbf, const float* grad_jb, float* grad_dist,
+                               float* grad_freq, float* freq_partials, void* stream);
+int gmp_sph_triplet_proj_fwd_f32(int64_t n_triplets, int64_t n_edges, int num_spherical,
+                                 int num_radial, const float* jb, const float* angle,
+                                 const float* torsion, const int64_t* idx_kj, const float* pref,
+                                 const float* w_sbf1_t, int n_layers, int ba, const float* w_t1_t,
+                                 int bt, float* S, float* P, void* stream);
+int gmp_sph_triplet_emb_f32(int64_t n_triplets, int64_t n_edges, int num_spherical,
+                            int num_radial, const float* jb, const float* angle,
+                            const float* torsion, const int64_t* idx_kj, const float* pref,
+                            float* angle_emb, float* torsion_emb, void* stream);
+int64_t gmp_sph_triplet_proj_bwd_partial_rows(int64_t n_triplets);
+int gmp_sph_triplet_proj_bwd_f32(int64_t n_triplets, int64_t n_edges, int num_spherical,
+                                 int num_radial, const float* jb, const float* angle,
+                                 const float* torsion, const int64_t* idx_kj, const float* pref,
+                                 const float* w_sbf1_t, int n_layers, int ba, const float* w_t1_t,
+                                 int bt, const float* grad_S, const float* grad_P,
+                                 float* grad_w, float* partials, float* grad_jb_rows,
+                                 float* grad_angle, float* grad_torsion, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * K19 SphereNet triplet interaction of one layer (spherenet_layer.py update_e.forward):
+ *   out[s, c] = sum_{p in [rowptr[s], rowptr[s+1])} src[gather_idx[t], c]
+ *               (W_sbf2 S_t)[c] (W_t2 P_t)[c],   t = perm ? perm[p] : p
+ * src (n_src, I), S (T, ba), P (T, bt), w_sbf2 (I, ba), w_t2 (I, bt), out (n_seg, I).  With
+ * rowptr = K11's triplet offsets, perm = NULL and gather_idx = idx_kj this is the message m;
+ * with the CSR of idx_kj and gather_idx = idx_ji, src = grad_m, it is grad_xd.  One wave per
+ * segment adds the triplets in order: no atomics, bit-identical between runs.  Empty segments
+ * give zero rows; an index out of range contributes nothing.
+ *   bwd (ba, bt <= 16): grad_S (T, ba), grad_P (T, bt) and grad_w (I ba + I bt) = [grad w_sbf2 |
+ *   grad w_t2] through partials (gmp_triplet_interact_bwd_partial_rows(E) rows of that width),
+ *   summed in a fixed order.
+ * ------------------------------------------------------------------------------------------ */
+int gmp_triplet_interact_fwd_f32(int64_t n_seg, int64_t n_src, int64_t n_triplets, int64_t I,
+                                 int ba, int bt, const float* src, const float* S, const float* P,
+                                 const float* w_sbf2, const float* w_t2, const int64_t* gather_idx,
+                                 const int64_t* perm, const int64_t* rowptr, float* out,
+                                 void* stream);
+int64_t gmp_triplet_interact_bwd_partial_rows(int64_t n_edges);
+int gmp_triplet_interact_bwd_f32(int64_t n_edges, int64_t n_triplets, int64_t I, int ba, int bt,
+                                 const float* grad_m, const float* xd, const float* S,
+                                 const float* P, const float* w_sbf2, const float* w_t2,
+                                 const int64_t* idx_kj, const int64_t* offsets, float* grad_S,
+                                 float* grad_P, float* grad_w, float* partials, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
