@@ -1891,6 +1891,180 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> triplet_interact_bwd(
   return {gS, gP, gw.narrow(0, 0, I * ba).view({I, ba}), gw.narrow(0, I * ba, I * bt).view({I, bt})};
 }
 
+// ------------------------------------------------------------------ K18d / K19d: DimeNet++
+std::tuple<Tensor, Tensor> dime_edge_basis_fwd(const Tensor& dist, const Tensor& freq,
+                                               const Tensor& zeros, const Tensor& norm,
+                                               double cutoff, int64_t envelope_exponent) {
+  OpGuard g(dist, "dime_edge_basis_fwd");
+  f32(dist, "dist");
+  f32(freq, "freq");
+  int64_t n, k;
+  sph_tables(zeros, norm, &n, &k);
+  TORCH_CHECK(dist.dim() == 1, "gmp.dime_edge_basis_fwd: dist (E)");
+  numel(freq, k, "freq");
+  const int64_t E = dist.numel();
+  Tensor rbf = at::empty({E, k}, dist.options()), sbe = at::empty({E, n * k}, dist.options());
+  check_rc(gmp_dime_edge_basis_fwd_f32(fp(dist), E, (float)cutoff, (int)envelope_exponent,
+                                       fp(freq), (int)k, fp(zeros), fp(norm), (int)n, fp(rbf),
+                                       fp(sbe), cur_stream()),
+           "gmp_dime_edge_basis_fwd_f32");
+  return {rbf, sbe};
+}
+
+std::tuple<Tensor, Tensor> dime_edge_basis_bwd(const Tensor& dist, const Tensor& freq,
+                                               const Tensor& zeros, const Tensor& norm,
+                                               double cutoff, int64_t envelope_exponent,
+                                               const optional<Tensor>& grad_rbf,
+                                               const optional<Tensor>& grad_sbe) {
+  OpGuard g(dist, "dime_edge_basis_bwd");
+  f32(dist, "dist");
+  f32(freq, "freq");
+  int64_t n, k;
+  sph_tables(zeros, norm, &n, &k);
+  TORCH_CHECK(dist.dim() == 1, "gmp.dime_edge_basis_bwd: dist (E)");
+  numel(freq, k, "freq");
+  const int64_t E = dist.numel();
+  opt_f32(grad_rbf, {E, k}, "grad_rbf");
+  opt_f32(grad_sbe, {E, n * k}, "grad_sbe");
+  Tensor gd = at::empty({E}, dist.options()), gf = at::empty({k}, dist.options());
+  Tensor part = at::empty({gmp_dime_edge_basis_bwd_partial_rows(E), k}, dist.options());
+  check_rc(gmp_dime_edge_basis_bwd_f32(fp(dist), E, (float)cutoff, (int)envelope_exponent,
+                                       fp(freq), (int)k, fp(zeros), fp(norm), (int)n,
+                                       cfp(grad_rbf), cfp(grad_sbe), fp(gd), fp(gf), fp(part),
+                                       cur_stream()),
+           "gmp_dime_edge_basis_bwd_f32");
+  return {gd, gf};
+}
+
+// shared argument checks of the per-triplet K18d entry points; returns T
+int64_t dime_triplet_args(const Tensor& sbe, const Tensor& angle, const Tensor& idx_kj,
+                          const Tensor& pref, int64_t n, int64_t k) {
+  f32(sbe, "sbe");
+  f32(angle, "angle");
+  i64(idx_kj, "idx_kj");
+  f32(pref, "pref");
+  TORCH_CHECK(n >= 1 && k >= 1 && sbe.dim() == 2 && sbe.size(1) == n * k,
+              "gmp: sbe (E, num_spherical * num_radial)");
+  numel(pref, n * n, "pref");
+  const int64_t T = angle.numel();
+  numel(idx_kj, T, "idx_kj");
+  return T;
+}
+
+void dime_proj_weights(const Tensor& wt, int64_t n, int64_t k, int64_t L, int64_t b) {
+  f32(wt, "w_sbf1_t");
+  TORCH_CHECK(L >= 1 && b >= 1, "gmp: n_layers, b >= 1");
+  shape(wt, {n * k, pad8(L * b)}, "w_sbf1_t");
+}
+
+Tensor dime_triplet_proj_fwd(const Tensor& sbe, const Tensor& angle, const Tensor& idx_kj,
+                             const Tensor& pref, const Tensor& wt, int64_t n, int64_t k,
+                             int64_t L, int64_t b) {
+  OpGuard g(sbe, "dime_triplet_proj_fwd");
+  const int64_t T = dime_triplet_args(sbe, angle, idx_kj, pref, n, k);
+  dime_proj_weights(wt, n, k, L, b);
+  Tensor S = at::empty({L, T, b}, sbe.options());
+  check_rc(gmp_dime_triplet_proj_fwd_f32(T, sbe.size(0), (int)n, (int)k, fp(sbe), fp(angle),
+                                         ip(idx_kj), fp(pref), fp(wt), (int)L, (int)b, fp(S),
+                                         cur_stream()),
+           "gmp_dime_triplet_proj_fwd_f32");
+  return S;
+}
+
+Tensor dime_triplet_emb(const Tensor& sbe, const Tensor& angle, const Tensor& idx_kj,
+                        const Tensor& pref, int64_t n, int64_t k) {
+  OpGuard g(sbe, "dime_triplet_emb");
+  const int64_t T = dime_triplet_args(sbe, angle, idx_kj, pref, n, k);
+  Tensor sbf = at::empty({T, n * k}, sbe.options());
+  check_rc(gmp_dime_triplet_emb_f32(T, sbe.size(0), (int)n, (int)k, fp(sbe), fp(angle),
+                                    ip(idx_kj), fp(pref), fp(sbf), cur_stream()),
+           "gmp_dime_triplet_emb_f32");
+  return sbf;
+}
+
+// (grad w_sbf1_t, grad_sbe_rows (T, n k), grad_angle (T)); the last two are empty without
+// want_geometry
+std::tuple<Tensor, Tensor, Tensor> dime_triplet_proj_bwd(
+    const Tensor& sbe, const Tensor& angle, const Tensor& idx_kj, const Tensor& pref,
+    const Tensor& wt, int64_t n, int64_t k, int64_t L, int64_t b, const Tensor& gS,
+    bool want_geometry) {
+  OpGuard g(sbe, "dime_triplet_proj_bwd");
+  const int64_t T = dime_triplet_args(sbe, angle, idx_kj, pref, n, k);
+  dime_proj_weights(wt, n, k, L, b);
+  f32(gS, "grad_S");
+  shape(gS, {L, T, b}, "grad_S");
+  auto o = sbe.options();
+  Tensor gw = at::empty_like(wt);
+  Tensor part = at::empty({gmp_dime_triplet_proj_bwd_partial_rows(T), wt.numel()}, o);
+  const int64_t Tg = want_geometry ? T : 0;
+  Tensor gsb = at::empty({Tg, n * k}, o), ga = at::empty({Tg}, o);
+  check_rc(gmp_dime_triplet_proj_bwd_f32(T, sbe.size(0), (int)n, (int)k, fp(sbe), fp(angle),
+                                         ip(idx_kj), fp(pref), fp(wt), (int)L, (int)b, fp(gS),
+                                         fp(gw), fp(part), fp(gsb), fp(ga), cur_stream()),
+           "gmp_dime_triplet_proj_bwd_f32");
+  return {gw, gsb, ga};
+}
+
+void interact1_args(const Tensor& S, const Tensor& w) {
+  f32(S, "S");
+  f32(w, "w_sbf2");
+  TORCH_CHECK(S.dim() == 2 && w.dim() == 2 && w.size(0) >= 1 && w.size(1) == S.size(1) &&
+                  S.size(1) >= 1,
+              "gmp: S (T, b), w_sbf2 (I, b)");
+}
+
+Tensor triplet_interact1_fwd(const Tensor& src, const Tensor& S, const Tensor& w,
+                             const Tensor& gidx, const optional<Tensor>& perm,
+                             const Tensor& rowptr) {
+  OpGuard g(src, "triplet_interact1_fwd");
+  f32(src, "src");
+  interact1_args(S, w);
+  i64(gidx, "gather_idx");
+  i64(rowptr, "rowptr");
+  const int64_t T = S.size(0), I = w.size(0);
+  TORCH_CHECK(src.dim() == 2 && src.size(1) == I, "gmp.triplet_interact1_fwd: src (n_src, I)");
+  numel(gidx, T, "gather_idx");
+  TORCH_CHECK(rowptr.numel() >= 1, "gmp.triplet_interact1_fwd: rowptr (n_seg + 1)");
+  const bool hp = perm.has_value() && perm->defined();
+  if (hp) {
+    i64(*perm, "perm");
+    numel(*perm, T, "perm");
+  }
+  const int64_t n_seg = rowptr.numel() - 1;
+  Tensor out = at::empty({n_seg, I}, src.options());
+  check_rc(gmp_triplet_interact1_fwd_f32(n_seg, src.size(0), T, I, (int)S.size(1), fp(src), fp(S),
+                                         fp(w), ip(gidx), hp ? ip(*perm) : nullptr, ip(rowptr),
+                                         fp(out), cur_stream()),
+           "gmp_triplet_interact1_fwd_f32");
+  return out;
+}
+
+std::tuple<Tensor, Tensor> triplet_interact1_bwd(const Tensor& gm, const Tensor& xd,
+                                                 const Tensor& S, const Tensor& w,
+                                                 const Tensor& idx_kj, const Tensor& offs) {
+  OpGuard g(gm, "triplet_interact1_bwd");
+  f32(gm, "grad_m");
+  f32(xd, "xd");
+  interact1_args(S, w);
+  i64(idx_kj, "idx_kj");
+  i64(offs, "offsets");
+  const int64_t T = S.size(0), I = w.size(0), b = S.size(1);
+  TORCH_CHECK(xd.dim() == 2 && xd.size(1) == I, "gmp.triplet_interact1_bwd: xd (E, I)");
+  const int64_t E = xd.size(0);
+  shape(gm, {E, I}, "grad_m");
+  numel(idx_kj, T, "idx_kj");
+  numel(offs, E + 1, "offsets");
+  TORCH_CHECK(b <= 16, "gmp.triplet_interact1_bwd: basis_emb_size <= 16");
+  auto o = gm.options();
+  Tensor gS = at::empty({T, b}, o), gw = at::empty({I, b}, o);
+  Tensor part = at::empty({gmp_triplet_interact1_bwd_partial_rows(E), I * b}, o);
+  check_rc(gmp_triplet_interact1_bwd_f32(E, T, I, (int)b, fp(gm), fp(xd), fp(S), fp(w),
+                                         ip(idx_kj), ip(offs), fp(gS), fp(gw), fp(part),
+                                         cur_stream()),
+           "gmp_triplet_interact1_bwd_f32");
+  return {gS, gw};
+}
+
 // ------------------------------------------------------------------ Meta (shape) kernels
 namespace meta {
 std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> csr_build(const Tensor& index, int64_t n_seg,
@@ -2228,6 +2402,40 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> triplet_interact_bwd(
     const Tensor& wt, const Tensor&, const Tensor&) {
   return {at::empty_like(S), at::empty_like(P), at::empty_like(wa), at::empty_like(wt)};
 }
+std::tuple<Tensor, Tensor> dime_edge_basis_fwd(const Tensor& dist, const Tensor&,
+                                               const Tensor& zeros, const Tensor&, double,
+                                               int64_t) {
+  return {at::empty({dist.numel(), zeros.size(1)}, dist.options()),
+          at::empty({dist.numel(), zeros.numel()}, dist.options())};
+}
+std::tuple<Tensor, Tensor> dime_edge_basis_bwd(const Tensor& dist, const Tensor& freq,
+                                               const Tensor&, const Tensor&, double, int64_t,
+                                               const optional<Tensor>&, const optional<Tensor>&) {
+  return {at::empty_like(dist), at::empty_like(freq)};
+}
+Tensor dime_triplet_proj_fwd(const Tensor& sbe, const Tensor& angle, const Tensor&, const Tensor&,
+                             const Tensor&, int64_t, int64_t, int64_t L, int64_t b) {
+  return at::empty({L, angle.numel(), b}, sbe.options());
+}
+Tensor dime_triplet_emb(const Tensor& sbe, const Tensor& angle, const Tensor&, const Tensor&,
+                        int64_t n, int64_t k) {
+  return at::empty({angle.numel(), n * k}, sbe.options());
+}
+std::tuple<Tensor, Tensor, Tensor> dime_triplet_proj_bwd(
+    const Tensor& sbe, const Tensor& angle, const Tensor&, const Tensor&, const Tensor& wt,
+    int64_t n, int64_t k, int64_t, int64_t, const Tensor&, bool want_geometry) {
+  const int64_t Tg = want_geometry ? angle.numel() : 0;
+  auto o = sbe.options();
+  return {at::empty_like(wt), at::empty({Tg, n * k}, o), at::empty({Tg}, o)};
+}
+Tensor triplet_interact1_fwd(const Tensor& src, const Tensor&, const Tensor& w, const Tensor&,
+                             const optional<Tensor>&, const Tensor& rowptr) {
+  return at::empty({rowptr.numel() - 1, w.size(0)}, src.options());
+}
+std::tuple<Tensor, Tensor> triplet_interact1_bwd(const Tensor&, const Tensor&, const Tensor& S,
+                                                 const Tensor& w, const Tensor&, const Tensor&) {
+  return {at::empty_like(S), at::empty_like(w)};
+}
 }  // namespace meta
 
 }  // namespace
@@ -2372,6 +2580,22 @@ TORCH_LIBRARY(gmp, m) {
   m.def("triplet_interact_bwd(Tensor grad_m, Tensor xd, Tensor S, Tensor P, Tensor w_sbf2, "
         "Tensor w_t2, Tensor idx_kj, Tensor offsets) -> (Tensor grad_S, Tensor grad_P, "
         "Tensor grad_w_sbf2, Tensor grad_w_t2)");
+  m.def("dime_edge_basis_fwd(Tensor dist, Tensor freq, Tensor zeros, Tensor norm, float cutoff, "
+        "int envelope_exponent) -> (Tensor rbf, Tensor sbe)");
+  m.def("dime_edge_basis_bwd(Tensor dist, Tensor freq, Tensor zeros, Tensor norm, float cutoff, "
+        "int envelope_exponent, Tensor? grad_rbf, Tensor? grad_sbe) -> "
+        "(Tensor grad_dist, Tensor grad_freq)");
+  m.def("dime_triplet_proj_fwd(Tensor sbe, Tensor angle, Tensor idx_kj, Tensor pref, "
+        "Tensor w_sbf1_t, int num_spherical, int num_radial, int n_layers, int b) -> Tensor");
+  m.def("dime_triplet_emb(Tensor sbe, Tensor angle, Tensor idx_kj, Tensor pref, "
+        "int num_spherical, int num_radial) -> Tensor");
+  m.def("dime_triplet_proj_bwd(Tensor sbe, Tensor angle, Tensor idx_kj, Tensor pref, "
+        "Tensor w_sbf1_t, int num_spherical, int num_radial, int n_layers, int b, Tensor grad_S, "
+        "bool want_geometry) -> (Tensor grad_w_sbf1_t, Tensor grad_sbe_rows, Tensor grad_angle)");
+  m.def("triplet_interact1_fwd(Tensor src, Tensor S, Tensor w_sbf2, Tensor gather_idx, "
+        "Tensor? perm, Tensor rowptr) -> Tensor");
+  m.def("triplet_interact1_bwd(Tensor grad_m, Tensor xd, Tensor S, Tensor w_sbf2, Tensor idx_kj, "
+        "Tensor offsets) -> (Tensor grad_S, Tensor grad_w_sbf2)");
 }
 
 #define GMP_IMPL(m, ns)                                                    \
@@ -2442,7 +2666,14 @@ TORCH_LIBRARY(gmp, m) {
   m.impl("sph_triplet_emb", ns sph_triplet_emb);                          \
   m.impl("sph_triplet_proj_bwd", ns sph_triplet_proj_bwd);                \
   m.impl("triplet_interact_fwd", ns triplet_interact_fwd);                \
-  m.impl("triplet_interact_bwd", ns triplet_interact_bwd);
+  m.impl("triplet_interact_bwd", ns triplet_interact_bwd);                \
+  m.impl("dime_edge_basis_fwd", ns dime_edge_basis_fwd);                  \
+  m.impl("dime_edge_basis_bwd", ns dime_edge_basis_bwd);                  \
+  m.impl("dime_triplet_proj_fwd", ns dime_triplet_proj_fwd);              \
+  m.impl("dime_triplet_emb", ns dime_triplet_emb);                        \
+  m.impl("dime_triplet_proj_bwd", ns dime_triplet_proj_bwd);              \
+  m.impl("triplet_interact1_fwd", ns triplet_interact1_fwd);              \
+  m.impl("triplet_interact1_bwd", ns triplet_interact1_bwd);
 
 TORCH_LIBRARY_IMPL(gmp, CUDA, m) { GMP_IMPL(m, ) }
 // CPU tensors reach the same implementations, whose device guard rejects them with the

@@ -18,6 +18,7 @@ from .gvp import GVP, GVPConv, GVPConvLayer, GVPGNNModel  # noqa: F401
 from .schnet import SchNetModel, CFConv, InteractionBlock  # noqa: F401
 from .spherenet import (SphereNetModel, emb, init, update_e, update_v,  # noqa: F401
                         ResidualLayer, dist_emb)
+from .dimenet import DimeNetPPModel  # noqa: F401
 from .ops import second_order  # noqa: F401
 from .forces import energy_and_forces  # noqa: F401
 
@@ -28,4 +29,5 @@ __all__ = ["scatter", "scatter_sum", "scatter_add", "scatter_mean", "scatter_max
            "SymmetricContraction", "first_node_pooling", "GVP", "GVPConv", "GVPConvLayer",
            "GVPGNNModel", "SchNetModel", "CFConv", "InteractionBlock", "second_order",
            "energy_and_forces", "radius_graph_gpu", "radius_graph_pbc_gpu", "pbc_grid_plan",
-           "SphereNetModel", "emb", "init", "update_e", "update_v", "ResidualLayer", "dist_emb"]
+           "SphereNetModel", "emb", "init", "update_e", "update_v", "ResidualLayer", "dist_emb",
+           "DimeNetPPModel"]

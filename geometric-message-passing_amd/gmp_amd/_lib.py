@@ -259,6 +259,21 @@ SIGNATURES = {
                                      + [c_vp] * 10),
     "gmp_triplet_interact_bwd_partial_rows": (c_i64, [c_i64]),
     "gmp_triplet_interact_bwd_f32": (c_int, [c_i64, c_i64, c_i64, c_int, c_int] + [c_vp] * 13),
+    # K18d / K19d: DimeNet++'s angle-only basis and one-factor triplet interaction; additions only
+    "gmp_dime_edge_basis_fwd_f32": (c_int, [c_vp, c_i64, c_f32, c_int, c_vp, c_int, c_vp, c_vp,
+                                            c_int, c_vp, c_vp, c_vp]),
+    "gmp_dime_edge_basis_bwd_partial_rows": (c_i64, [c_i64]),
+    "gmp_dime_edge_basis_bwd_f32": (c_int, [c_vp, c_i64, c_f32, c_int, c_vp, c_int, c_vp, c_vp,
+                                            c_int] + [c_vp] * 6),
+    "gmp_dime_triplet_proj_fwd_f32": (c_int, [c_i64, c_i64, c_int, c_int] + [c_vp] * 5
+                                      + [c_int, c_int, c_vp, c_vp]),
+    "gmp_dime_triplet_emb_f32": (c_int, [c_i64, c_i64, c_int, c_int] + [c_vp] * 6),
+    "gmp_dime_triplet_proj_bwd_partial_rows": (c_i64, [c_i64]),
+    "gmp_dime_triplet_proj_bwd_f32": (c_int, [c_i64, c_i64, c_int, c_int] + [c_vp] * 5
+                                      + [c_int, c_int] + [c_vp] * 6),
+    "gmp_triplet_interact1_fwd_f32": (c_int, [c_i64, c_i64, c_i64, c_i64, c_int] + [c_vp] * 8),
+    "gmp_triplet_interact1_bwd_partial_rows": (c_i64, [c_i64]),
+    "gmp_triplet_interact1_bwd_f32": (c_int, [c_i64, c_i64, c_i64, c_int] + [c_vp] * 10),
 }
 
 # include/gmp.h GMP_ABI_VERSION (6: r06 — K17 gmp_gvp_ff_{fwd,bwd}_f32, K15b gmp_egnn_node_bwd_f32;

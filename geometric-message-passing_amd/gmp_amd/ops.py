@@ -1547,6 +1547,108 @@ class TripletInteractFn(torch.autograd.Function):
         return gxd, gS, gP, gWa, gWt, None, None, None
 
 
+# ----------------------------------------------------------------------------------- DimeNet++
+class DimeEdgeBasisFn(torch.autograd.Function):
+    """(rbf (E, k), sbe (E, n k)) of K18d gmp_dime_edge_basis_*: env(x) sin(freq x) and
+    env(x) N_lq j_l(z_lq x), x = dist / cutoff, env the envelope cut to zero at and beyond the
+    cutoff (PyG's [x < 1]).  Gradients reach dist and freq."""
+
+    @staticmethod
+    def forward(ctx, dist, freq, zeros, norm, cutoff, envelope_exponent):
+        dist, freq = _f32c(dist), _f32c(freq)
+        _need_cuda(dist, freq, zeros, norm)
+        ctx.save_for_backward(dist, freq, zeros, norm)
+        ctx.cutoff, ctx.p = float(cutoff), int(envelope_exponent)
+        return _lib.torch_ops().dime_edge_basis_fwd(dist, freq, zeros, norm, ctx.cutoff, ctx.p)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_rbf, g_sbe):
+        dist, freq, zeros, norm = ctx.saved_tensors
+        g_rbf = _f32c(g_rbf) if g_rbf is not None else None
+        g_sbe = _f32c(g_sbe) if g_sbe is not None else None
+        gd, gf = _lib.torch_ops().dime_edge_basis_bwd(dist, freq, zeros, norm, ctx.cutoff, ctx.p,
+                                                      g_rbf, g_sbe)
+        return gd, gf, None, None, None, None
+
+
+class DimeTripletProjFn(torch.autograd.Function):
+    """K18d gmp_dime_triplet_proj_*: S[l] = W_sbf1[l] sbf for every layer l at once, sbf_t =
+    sbe[idx_kj[t]] * Y_l0(angle_t) formed on chip.  Returns (S[0], .., S[L-1]).  Gradients: the
+    L weights and, where asked for, sbe (summed per edge over the CSR of idx_kj) and angle."""
+
+    @staticmethod
+    def forward(ctx, sbe, angle, idx_kj, pref, n, k, L, *weights):
+        sbe, angle, idx_kj = _f32c(sbe), _f32c(angle), _i64c(idx_kj)
+        _need_cuda(sbe, angle, idx_kj, pref, *weights)
+        b = weights[0].shape[0]
+        wt = sph_feature_major(weights, n * k)
+        S = _lib.torch_ops().dime_triplet_proj_fwd(sbe, angle, idx_kj, pref, wt, n, k, L, b)
+        ctx.save_for_backward(sbe, angle, idx_kj, pref, wt)
+        ctx.dims = (n, k, L, b)
+        return tuple(S.unbind(0))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        sbe, angle, idx_kj, pref, wt = ctx.saved_tensors
+        n, k, L, b = ctx.dims
+        T = angle.numel()
+        gS = sbe.new_zeros((L, T, b))
+        for l, g in enumerate(grads):
+            if g is not None:
+                gS[l] = g
+        geom = any(ctx.needs_input_grad[:2])
+        gw, gsbe_rows, ga = _lib.torch_ops().dime_triplet_proj_bwd(sbe, angle, idx_kj, pref, wt,
+                                                                   n, k, L, b, gS, geom)
+        gsbe = None
+        if geom and T == 0:
+            gsbe = torch.zeros_like(sbe)
+        elif geom:
+            gsbe, _ = segment_reduce(gsbe_rows, get_csr(idx_kj, sbe.shape[0]), "sum")
+        else:
+            ga = None
+        gws = [gw[:, l * b:(l + 1) * b].t().contiguous() for l in range(L)]
+        return (gsbe, ga, None, None, None, None, None) + tuple(gws)
+
+
+def dime_triplet_embeddings(sbe, angle, idx_kj, pref, n, k):
+    """The materialised sbf (T, n k) of K18d (tests and the composed baseline; the model never
+    forms it)."""
+    _need_cuda(sbe, angle, idx_kj, pref)
+    return _lib.torch_ops().dime_triplet_emb(_f32c(sbe), _f32c(angle), _i64c(idx_kj), pref, n, k)
+
+
+class TripletInteract1Fn(torch.autograd.Function):
+    """K19d gmp_triplet_interact1_*: m[e] = sum over the triplets t of edge e (the contiguous
+    range [offsets[e], offsets[e+1]) that K11 emits) of xd[idx_kj[t]] * (W_sbf2 S_t).
+    Deterministic both ways; grad_xd runs the same kernel over the CSR of idx_kj."""
+
+    @staticmethod
+    def forward(ctx, xd, S, W, idx_kj, idx_ji, offsets):
+        xd, S, W = _f32c(xd), _f32c(S), _f32c(W)
+        idx_kj, idx_ji, offsets = _i64c(idx_kj), _i64c(idx_ji), _i64c(offsets)
+        _need_cuda(xd, S, W, idx_kj, idx_ji, offsets)
+        ctx.save_for_backward(xd, S, W, idx_kj, idx_ji, offsets)
+        return _lib.torch_ops().triplet_interact1_fwd(xd, S, W, idx_kj, None, offsets)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gm):
+        xd, S, W, idx_kj, idx_ji, offsets = ctx.saved_tensors
+        gm = _f32c(gm)
+        tops = _lib.torch_ops()
+        gS, gW = tops.triplet_interact1_bwd(gm, xd, S, W, idx_kj, offsets)
+        gxd = None
+        if ctx.needs_input_grad[0]:
+            if idx_kj.numel() == 0 or xd.shape[0] == 0:
+                gxd = torch.zeros_like(xd)
+            else:
+                csr = get_csr(idx_kj, xd.shape[0])
+                gxd = tops.triplet_interact1_fwd(gm, S, W, idx_ji, csr.perm, csr.rowptr)
+        return gxd, gS, gW, None, None, None
+
+
 class FirstOrderOnlyFn(torch.autograd.Function):
     """Identity whose gradient raises when it is differentiated again (create_graph=True)
     instead of passing as a constant: K11's geometry backward records no graph, and the

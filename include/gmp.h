@@ -1093,6 +1093,76 @@ int gmp_triplet_interact_bwd_f32(int64_t n_edges, int64_t n_triplets, int64_t I,
                                  const int64_t* idx_kj, const int64_t* offsets, float* grad_S,
                                  float* grad_P, float* grad_w, float* partials, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K18d DimeNet++ basis (PyG DimeNetPlusPlus: BesselBasisLayer, SphericalBasisLayer), the
+ * angle-only form of K18.  Additions only: the ABI version is unchanged.  Tables as K18.
+ *
+ * Edge basis, x = dist / cutoff, env(x) = envelope(x) [x < 1] (K18's envelope, cut to zero at
+ * and beyond the cutoff):
+ *   rbf (E, k)   = env(x) sin(freq_q x)
+ *   sbe (E, n k) = env(x) N_lq j_l(z_lq x)     (j_l by series / recurrence, in double)
+ *   An edge with x >= 1 gives exact zero rows and, in bwd, an exact zero grad_dist.
+ *   bwd: as gmp_sph_edge_basis_bwd_f32 (grad_freq through ordered partials, no atomics).
+ *
+ * Triplet projection for L layers at once, sbf_t[l k + q] = sbe[idx_kj[t]][l k + q]
+ * Y_l0(angle_t) (only the n Legendre values of a triplet are formed; never written):
+ *   S (L, T, b) = W_sbf1[l] sbf_t,   w_sbf1_t (n k, ld) feature-major, column layer * b + j,
+ *   ld = L b rounded up to a multiple of 8, padding zero.
+ *   bwd: grad_w (n k ld) through partials (gmp_dime_triplet_proj_bwd_partial_rows(T) rows of
+ *        that width), summed in a fixed order.  If grad_sbe_rows (T, n k) and grad_angle (T)
+ *        are given (both or neither) the geometry gradients are written too; the caller sums
+ *        grad_sbe_rows per edge over the CSR of idx_kj.
+ *   emb: the materialised sbf (T, n k) (tests, baselines).
+ * An idx_kj outside [0, E) contributes a zero row.
+ * ------------------------------------------------------------------------------------------ */
+int gmp_dime_edge_basis_fwd_f32(const float* dist, int64_t n_edges, float cutoff,
+                                int envelope_exponent, const float* freq, int num_radial,
+                                const float* zeros, const float* norm, int num_spherical,
+                                float* rbf, float* sbe, void* stream);
+int64_t gmp_dime_edge_basis_bwd_partial_rows(int64_t n_edges);
+int gmp_dime_edge_basis_bwd_f32(const float* dist, int64_t n_edges, float cutoff,
+                                int envelope_exponent, const float* freq, int num_radial,
+                                const float* zeros, const float* norm, int num_spherical,
+                                const float* grad_rbf, const float* grad_sbe, float* grad_dist,
+                                float* grad_freq, float* freq_partials, void* stream);
+int gmp_dime_triplet_proj_fwd_f32(int64_t n_triplets, int64_t n_edges, int num_spherical,
+                                  int num_radial, const float* sbe, const float* angle,
+                                  const int64_t* idx_kj, const float* pref, const float* w_sbf1_t,
+                                  int n_layers, int b, float* S, void* stream);
+int gmp_dime_triplet_emb_f32(int64_t n_triplets, int64_t n_edges, int num_spherical,
+                             int num_radial, const float* sbe, const float* angle,
+                             const int64_t* idx_kj, const float* pref, float* sbf, void* stream);
+int64_t gmp_dime_triplet_proj_bwd_partial_rows(int64_t n_triplets);
+int gmp_dime_triplet_proj_bwd_f32(int64_t n_triplets, int64_t n_edges, int num_spherical,
+                                  int num_radial, const float* sbe, const float* angle,
+                                  const int64_t* idx_kj, const float* pref, const float* w_sbf1_t,
+                                  int n_layers, int b, const float* grad_S, float* grad_w,
+                                  float* partials, float* grad_sbe_rows, float* grad_angle,
+                                  void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * K19d DimeNet++ triplet interaction of one layer (InteractionPPBlock), K19 with one factor:
+ *   out[s, c] = sum_{p in [rowptr[s], rowptr[s+1])} src[gather_idx[t], c] (W_sbf2 S_t)[c],
+ *   t = perm ? perm[p] : p
+ * src (n_src, I), S (T, b), w_sbf2 (I, b), out (n_seg, I); rowptr / perm / gather_idx as K19
+ * (the message m, or grad_xd over the CSR of idx_kj).  One wave per segment, fixed order.
+ *   bwd (b <= 16, any I >= 1): grad_S (T, b) and grad_w (I, b) through partials
+ *   (gmp_triplet_interact1_bwd_partial_rows(E) rows of I b), summed in wave order.  The weight
+ *   gradient accumulators live in registers (lane = channel, 64 channels per pass).
+ *   GMP_ERR_UNSUPPORTED when I b floats exceed the forward's LDS cap; GMP_OK and a zero grad_w
+ *   at E = 0 or T = 0.
+ * ------------------------------------------------------------------------------------------ */
+int gmp_triplet_interact1_fwd_f32(int64_t n_seg, int64_t n_src, int64_t n_triplets, int64_t I,
+                                  int b, const float* src, const float* S, const float* w_sbf2,
+                                  const int64_t* gather_idx, const int64_t* perm,
+                                  const int64_t* rowptr, float* out, void* stream);
+int64_t gmp_triplet_interact1_bwd_partial_rows(int64_t n_edges);
+int gmp_triplet_interact1_bwd_f32(int64_t n_edges, int64_t n_triplets, int64_t I, int b,
+                                  const float* grad_m, const float* xd, const float* S,
+                                  const float* w_sbf2, const int64_t* idx_kj,
+                                  const int64_t* offsets, float* grad_S, float* grad_w,
+                                  float* partials, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
