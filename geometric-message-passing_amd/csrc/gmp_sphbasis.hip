@@ -1,20 +1,28 @@
-// K18: SphereNet's spherical basis (models/layers/spherenet_layer.py: dist_emb, angle_emb,
-// torsion_emb) without the per-triplet embeddings in HBM.
+// K18 / K18d: the spherical bases of SphereNet (models/layers/spherenet_layer.py: dist_emb,
+// angle_emb, torsion_emb) and DimeNet++ (PyG 2.3.1 DimeNetPlusPlus: BesselBasisLayer,
+// SphericalBasisLayer) without the per-triplet embeddings in HBM.  One set of kernels, each
+// instantiated twice:
 //
-// Per edge (gmp_sph_edge_basis_*): rbf[q] = envelope(x) sin(freq_q x) and jb[l, q] =
-// N_lq j_l(z_lq x), x = d / cutoff.  The reference evaluates j_l by its closed form
-// (sin / cos over powers of x), which cancels catastrophically for small arguments: j_6 at
-// x = 0.05 comes out as -0.6 in fp32 where the value is ~1e-9.  Here j_l is a power series
-// below x = l + 1 (all terms after the first few decrease, no cancellation) and the upward
-// recurrence from j_0, j_1 above (stable for x > l).  E is small next to T, so the per-edge
-// arithmetic runs in double and is rounded once.
+//   kCut (per edge):        false = SphereNet, true = DimeNet++
+//   kTorsion (per triplet): true = SphereNet (angle and torsion features), false = DimeNet++
+//                           (angle features only)
 //
-// Per triplet (gmp_sph_triplet_proj_*): the n k angle features jb[kj][l, q] Y_l0(theta) and the
-// n^2 k torsion features jb[kj][b, q] Yflat[a n + b](theta, phi) are formed in LDS from the
-// gathered jb row and the n^2 real harmonics of the triplet, and multiplied at once into the
-// first projections of every layer: S (L, T, ba), P (L, T, bt).  The reference's layout is kept:
-// per l the harmonics are ordered m = 0, 1..l (cos), -l..-1 (sin), and the view(-1, n, n, 1)
-// of torsion_emb pairs Bessel order b with flat harmonic a n + b.
+// Per edge (gmp_sph_edge_basis_*, gmp_dime_edge_basis_*): rbf[q] = envelope(x) sin(freq_q x) and
+// jb[l, q] = N_lq j_l(z_lq x), x = d / cutoff.  With kCut the envelope is also multiplied into
+// jb (PyG's sbf), and values and gradients are exactly zero at and beyond the cutoff (PyG's
+// [x < 1]).  The reference evaluates j_l by its closed form (sin / cos over powers of x), which
+// cancels catastrophically for small arguments: j_6 at x = 0.05 comes out as -0.6 in fp32 where
+// the value is ~1e-9.  Here j_l is a power series below x = l + 1 (all terms after the first few
+// decrease, no cancellation) and the upward recurrence from j_0, j_1 above (stable for x > l).
+// E is small next to T, so the per-edge arithmetic runs in double and is rounded once.
+//
+// Per triplet (gmp_sph_triplet_proj_*, gmp_dime_triplet_proj_*): the n k angle features
+// jb[kj][l, q] Y_l0(theta) and, with kTorsion, the n^2 k torsion features jb[kj][b, q]
+// Yflat[a n + b](theta, phi) are formed in LDS from the gathered jb row and the harmonics of the
+// triplet, and multiplied at once into the first projections of every layer: S (L, T, ba),
+// P (L, T, bt).  The reference's layout is kept: per l the harmonics are ordered m = 0, 1..l
+// (cos), -l..-1 (sin), and the view(-1, n, n, 1) of torsion_emb pairs Bessel order b with flat
+// harmonic a n + b.  Without kTorsion only the n values Y_l0 are formed and staged (row l).
 #include <algorithm>
 
 #include "gmp_common.h"
@@ -25,8 +33,13 @@ namespace {
 constexpr int kTile = 64;        // triplets per tile (one per lane)
 constexpr int kLd = kTile + 1;   // LDS row stride of the staged [feature][triplet] planes
 constexpr int kOC = 8;           // output columns per accumulator chunk
-constexpr int kProjBwdBlocks = 512;
 constexpr int kEdgeT = 256;
+constexpr size_t kLdsCap = 60 * 1024;
+// Grid caps of the weight-gradient kernel; they fix the order of the partial sums.  Without the
+// torsion features its blocks are one wave at the default basis (n k = 42 features <= 64), so the
+// grid is what fills the chip: 4096 blocks (0.69 ms at 3.5M triplets; 2.29 ms at 512).
+constexpr int kProjBwdBlocks = 512;
+constexpr int kProjBwdBlocksAngleOnly = 4096;
 
 // j_l(x) for x > 0
 __device__ double sph_jl(int l, double x) {
@@ -60,34 +73,26 @@ __device__ double sph_jl_prime(int l, double x) {
   return sph_jl(l - 1, x) - (double)(l + 1) / x * sph_jl(l, x);
 }
 
-struct Env {
-  double a, b, c;
-  int p;
-};
-__device__ Env make_env(int exponent) {
-  Env e;
-  e.p = exponent + 1;
-  e.a = -(double)(e.p + 1) * (e.p + 2) / 2.0;
-  e.b = (double)e.p * (e.p + 2);
-  e.c = -(double)e.p * (e.p + 1) / 2.0;
-  return e;
-}
 __device__ double ipow(double x, int n) {
   double r = 1.0;
   for (int i = 0; i < n; ++i) r *= x;
   return r;
 }
+
 // envelope(x) = 1/x + a x^(p-1) + b x^p + c x^(p+1) and its derivative
-__device__ void env_eval(const Env& e, double x, double* v, double* dv) {
-  const double x0 = ipow(x, e.p - 1);
+__device__ void env_eval(int exponent, double x, double* v, double* dv) {
+  const int p = exponent + 1;
+  const double a = -(double)(p + 1) * (p + 2) / 2.0, b = (double)p * (p + 2),
+               c = -(double)p * (p + 1) / 2.0;
+  const double x0 = ipow(x, p - 1);
   const double x1 = x0 * x, x2 = x1 * x;
-  *v = 1.0 / x + e.a * x0 + e.b * x1 + e.c * x2;
-  const double xm = e.p >= 2 ? ipow(x, e.p - 2) : 0.0;
-  *dv = -1.0 / (x * x) + e.a * (double)(e.p - 1) * xm + e.b * (double)e.p * x0 +
-        e.c * (double)(e.p + 1) * x1;
+  *v = 1.0 / x + a * x0 + b * x1 + c * x2;
+  const double xm = p >= 2 ? ipow(x, p - 2) : 0.0;
+  *dv = -1.0 / (x * x) + a * (double)(p - 1) * xm + b * (double)p * x0 + c * (double)(p + 1) * x1;
 }
 
 // thread per (edge, column), columns [0, k) = rbf, [k, k + n k) = jb
+template <bool kCut>
 __global__ __launch_bounds__(kEdgeT) void edge_basis_fwd(
     const float* __restrict__ dist, int64_t E, float cutoff, int exponent,
     const float* __restrict__ freq, int k, const float* __restrict__ zeros,
@@ -98,18 +103,26 @@ __global__ __launch_bounds__(kEdgeT) void edge_basis_fwd(
   const int64_t e = i / cols;
   const int c = (int)(i - e * cols);
   const double x = (double)dist[e] / (double)cutoff;
-  if (c < k) {
-    double v, dv;
-    env_eval(make_env(exponent), x, &v, &dv);
-    rbf[e * k + c] = (float)(v * sin((double)freq[c] * x));
-  } else {
-    const int lq = c - k;
-    jb[e * nk + lq] = (float)((double)norm[lq] * sph_jl(lq / k, (double)zeros[lq] * x));
+  float out = 0.f;
+  if (!kCut || x < 1.0) {
+    double v = 0.0, dv = 0.0;
+    if (kCut || c < k) env_eval(exponent, x, &v, &dv);
+    if (c < k) {
+      out = (float)(v * sin((double)freq[c] * x));
+    } else {
+      const int lq = c - k;
+      const double scale = kCut ? v * (double)norm[lq] : (double)norm[lq];
+      out = (float)(scale * sph_jl(lq / k, (double)zeros[lq] * x));
+    }
   }
+  if (c < k) rbf[e * k + c] = out;
+  else jb[e * nk + (c - k)] = out;
 }
 
 // thread per edge: g_dist[e]; the freq gradient of the block's edges is tree-summed in LDS in
-// a fixed order into one partial row per block.
+// a fixed order into one partial row per block.  With kCut an edge at or beyond the cutoff is
+// dead: it is evaluated at x = 0.5 to stay finite and contributes exact zeros.
+template <bool kCut>
 __global__ __launch_bounds__(kEdgeT) void edge_basis_bwd(
     const float* __restrict__ dist, int64_t E, float cutoff, int exponent,
     const float* __restrict__ freq, int k, const float* __restrict__ zeros,
@@ -118,11 +131,13 @@ __global__ __launch_bounds__(kEdgeT) void edge_basis_bwd(
     float* __restrict__ freq_partials) {
   __shared__ float red[kEdgeT];
   const int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  const bool live = e < E;
-  const double x = live ? (double)dist[e] / (double)cutoff : 1.0;
+  const bool in_range = e < E;
+  const double xr = in_range ? (double)dist[e] / (double)cutoff : 1.0;
+  const bool live = in_range && (!kCut || xr < 1.0);
+  const double x = kCut && !live ? 0.5 : xr;
   const double inv_c = 1.0 / (double)cutoff;
   double env = 0.0, denv = 0.0;
-  env_eval(make_env(exponent), x, &env, &denv);
+  env_eval(exponent, x, &env, &denv);
   double gd = 0.0;
   for (int q = 0; q < k; ++q) {
     float contrib = 0.f;
@@ -142,14 +157,35 @@ __global__ __launch_bounds__(kEdgeT) void edge_basis_bwd(
     if (threadIdx.x == 0) freq_partials[(int64_t)blockIdx.x * k + q] = red[0];
     __syncthreads();
   }
-  if (!live) return;
-  if (g_jb) {
+  if (!in_range) return;
+  if (live && g_jb) {
     for (int lq = 0; lq < nk; ++lq) {
       const double z = (double)zeros[lq];
-      gd += (double)g_jb[e * nk + lq] * (double)norm[lq] * z * inv_c * sph_jl_prime(lq / k, z * x);
+      const int l = lq / k;
+      if constexpr (kCut) {
+        gd += (double)g_jb[e * nk + lq] * (double)norm[lq] * inv_c *
+              (denv * sph_jl(l, z * x) + env * z * sph_jl_prime(l, z * x));
+      } else {
+        gd += (double)g_jb[e * nk + lq] * (double)norm[lq] * z * inv_c * sph_jl_prime(l, z * x);
+      }
     }
   }
-  g_dist[e] = (float)gd;
+  g_dist[e] = live ? (float)gd : 0.f;
+}
+
+// the staged harmonics: row of Y_l0, and the number of rows
+template <bool kTorsion>
+__host__ __device__ constexpr int y_row(int l) {
+  return kTorsion ? l * l : l;
+}
+template <bool kTorsion>
+__host__ __device__ constexpr int y_planes(int n) {
+  return kTorsion ? n * n : n;
+}
+
+// element (t, o) of the (L, T, b) layout of S / P and their gradients, o = layer * b + j
+__device__ __forceinline__ int64_t proj_index(int o, int64_t t, int64_t T, int b) {
+  return ((int64_t)(o / b) * T + t) * b + o % b;
 }
 
 // The n^2 real harmonics of one direction, flat index l^2 + p with p = 0 (m = 0), 1..l (cos m
@@ -157,8 +193,9 @@ __global__ __launch_bounds__(kEdgeT) void edge_basis_bwd(
 // C_m + i S_m = (sin theta e^{i phi})^m and P_l^m the polynomial part of the associated
 // Legendre function (the sin^m theta factor lives in C_m, S_m), built by the recurrences of
 // the reference's generator; pref carries the sqrt(2) of m != 0.
+// Without kTorsion only m = 0 runs (the Legendre recurrence; phi is not read) and Y_l0 is row l.
 // kGrad: instead of storing Y, returns sum_idx gY[idx] dY[idx]/dtheta and /dphi.
-template <bool kGrad>
+template <bool kGrad, bool kTorsion>
 __device__ void sph_harmonics(int n, float theta, float phi, const float* __restrict__ pref,
                               float* Y, int stride, float* g_theta, float* g_phi) {
   float st, ct, sp, cp;
@@ -169,7 +206,7 @@ __device__ void sph_harmonics(int n, float theta, float phi, const float* __rest
   float C = 1.f, S = 0.f, dCt = 0.f, dSt = 0.f;
   float pmm = 1.f;  // P_m^m = (-1)^m (2m - 1)!!
   float gt = 0.f, gp = 0.f;
-  for (int m = 0; m < n; ++m) {
+  for (int m = 0; m < (kTorsion ? n : 1); ++m) {
     if (m > 0) {
       const float C1 = x * C - y * S, S1 = x * S + y * C;
       const float dC1 = dxt * C + x * dCt - dyt * S - y * dSt;
@@ -194,8 +231,9 @@ __device__ void sph_harmonics(int n, float theta, float phi, const float* __rest
       const int base = l * l;
       if (m == 0) {
         const float f = pref[base];
-        if (kGrad) gt += Y[base * stride] * f * dp * (-st);
-        else Y[base * stride] = f * p;
+        const int i0 = y_row<kTorsion>(l);
+        if (kGrad) gt += Y[i0 * stride] * f * dp * (-st);
+        else Y[i0 * stride] = f * p;
       } else {
         const int ic = base + m, is = base + 2 * l + 1 - m;
         const float fc = pref[ic], fs = pref[is];
@@ -215,6 +253,7 @@ __device__ void sph_harmonics(int n, float theta, float phi, const float* __rest
 
 // Stage one tile: jbL[c * kLd + r] = jb[idx_kj[t0 + r], c] (coalesced rows), YL[idx * kLd + r].
 // kjL (kTile ints) is scratch.  All threads of the block take part; ends with a barrier.
+template <bool kTorsion>
 __device__ void stage_tile(int64_t t0, int64_t T, int64_t E, int n, int nk,
                            const float* __restrict__ jb,
                            const float* __restrict__ angle, const float* __restrict__ torsion,
@@ -233,10 +272,10 @@ __device__ void stage_tile(int64_t t0, int64_t T, int64_t E, int n, int nk,
   }
   if (tid < kTile) {
     if (t0 + tid < T) {
-      sph_harmonics<false>(n, angle[t0 + tid], torsion[t0 + tid], pref, YL + tid, kLd, nullptr,
-                           nullptr);
+      sph_harmonics<false, kTorsion>(n, angle[t0 + tid], kTorsion ? torsion[t0 + tid] : 0.f, pref,
+                                     YL + tid, kLd, nullptr, nullptr);
     } else {
-      for (int i = 0; i < n * n; ++i) YL[i * kLd + tid] = 0.f;
+      for (int i = 0; i < y_planes<kTorsion>(n); ++i) YL[i * kLd + tid] = 0.f;
     }
   }
   __syncthreads();
@@ -244,29 +283,32 @@ __device__ void stage_tile(int64_t t0, int64_t T, int64_t E, int n, int nk,
 
 // one wave per tile, lane = triplet.  w1t (n k, oa_ld), w2t (n^2 k, ot_ld): feature-major,
 // columns o = layer * b + j, leading dimensions padded to a multiple of kOC with zeros.
+// The arguments that only kTorsion reads (torsion, w2t, Ot, ot_ld, bt, P) come last, here and in
+// the kernels below: the angle-only instantiation then loads a prefix of the argument block and
+// nothing of the rest (the order changes its prologue, and with it the measured time by 2-6 %).
+template <bool kTorsion>
 __global__ __launch_bounds__(kTile) void triplet_proj_fwd(
     int64_t T, int64_t E, int n, int k, const float* __restrict__ jb,
-    const float* __restrict__ angle,
-    const float* __restrict__ torsion, const int64_t* __restrict__ idx_kj,
+    const float* __restrict__ angle, const int64_t* __restrict__ idx_kj,
     const float* __restrict__ pref, const float* __restrict__ w1t, int Oa, int oa_ld, int ba,
-    const float* __restrict__ w2t, int Ot, int ot_ld, int bt, float* __restrict__ S,
-    float* __restrict__ P) {
+    float* __restrict__ S, const float* __restrict__ torsion, const float* __restrict__ w2t,
+    int Ot, int ot_ld, int bt, float* __restrict__ P) {
   extern __shared__ float sm[];
   __shared__ int64_t kjL[kTile];
-  const int nk = n * k, nn = n * n;
+  const int nk = n * k;
   float* jbL = sm;
   float* YL = sm + nk * kLd;
   const int lane = threadIdx.x;
   for (int64_t t0 = (int64_t)blockIdx.x * kTile; t0 < T; t0 += (int64_t)gridDim.x * kTile) {
     __syncthreads();
-    stage_tile(t0, T, E, n, nk, jb, angle, torsion, idx_kj, pref, jbL, YL, kjL);
+    stage_tile<kTorsion>(t0, T, E, n, nk, jb, angle, torsion, idx_kj, pref, jbL, YL, kjL);
     const int64_t t = t0 + lane;
     for (int o0 = 0; o0 < Oa; o0 += kOC) {
       float acc[kOC];
 #pragma unroll
       for (int u = 0; u < kOC; ++u) acc[u] = 0.f;
       for (int l = 0; l < n; ++l) {
-        const float y = YL[l * l * kLd + lane];
+        const float y = YL[y_row<kTorsion>(l) * kLd + lane];
         for (int q = 0; q < k; ++q) {
           const int f = l * k + q;
           const float e = jbL[f * kLd + lane] * y;
@@ -279,91 +321,98 @@ __global__ __launch_bounds__(kTile) void triplet_proj_fwd(
 #pragma unroll
         for (int u = 0; u < kOC; ++u) {
           const int o = o0 + u;
-          if (o < Oa) S[((int64_t)(o / ba) * T + t) * ba + o % ba] = acc[u];
+          if (o < Oa) S[proj_index(o, t, T, ba)] = acc[u];
         }
       }
     }
-    for (int o0 = 0; o0 < Ot; o0 += kOC) {
-      float acc[kOC];
+    if constexpr (kTorsion) {
+      for (int o0 = 0; o0 < Ot; o0 += kOC) {
+        float acc[kOC];
 #pragma unroll
-      for (int u = 0; u < kOC; ++u) acc[u] = 0.f;
-      for (int ab = 0; ab < nn; ++ab) {
-        const float y = YL[ab * kLd + lane];
-        const int b = ab % n;
-        for (int q = 0; q < k; ++q) {
-          const float e = jbL[(b * k + q) * kLd + lane] * y;
-          const float* w = w2t + ((int64_t)ab * k + q) * ot_ld + o0;
+        for (int u = 0; u < kOC; ++u) acc[u] = 0.f;
+        for (int ab = 0; ab < n * n; ++ab) {
+          const float y = YL[ab * kLd + lane];
+          const int b = ab % n;
+          for (int q = 0; q < k; ++q) {
+            const float e = jbL[(b * k + q) * kLd + lane] * y;
+            const float* w = w2t + ((int64_t)ab * k + q) * ot_ld + o0;
 #pragma unroll
-          for (int u = 0; u < kOC; ++u) acc[u] = fmaf(w[u], e, acc[u]);
+            for (int u = 0; u < kOC; ++u) acc[u] = fmaf(w[u], e, acc[u]);
+          }
         }
-      }
-      if (t < T) {
+        if (t < T) {
 #pragma unroll
-        for (int u = 0; u < kOC; ++u) {
-          const int o = o0 + u;
-          if (o < Ot) P[((int64_t)(o / bt) * T + t) * bt + o % bt] = acc[u];
+          for (int u = 0; u < kOC; ++u) {
+            const int o = o0 + u;
+            if (o < Ot) P[proj_index(o, t, T, bt)] = acc[u];
+          }
         }
       }
     }
   }
 }
 
-// the materialising form: angle_emb (T, n k), torsion_emb (T, n^2 k)
+// the materialising form: angle_emb (T, n k) and, with kTorsion, torsion_emb (T, n^2 k)
+template <bool kTorsion>
 __global__ __launch_bounds__(kTile) void triplet_emb(
     int64_t T, int64_t E, int n, int k, const float* __restrict__ jb,
-    const float* __restrict__ angle,
-    const float* __restrict__ torsion, const int64_t* __restrict__ idx_kj,
-    const float* __restrict__ pref, float* __restrict__ aemb, float* __restrict__ temb) {
+    const float* __restrict__ angle, const int64_t* __restrict__ idx_kj,
+    const float* __restrict__ pref, float* __restrict__ aemb,
+    const float* __restrict__ torsion, float* __restrict__ temb) {
   extern __shared__ float sm[];
   __shared__ int64_t kjL[kTile];
-  const int nk = n * k, nnk = n * n * k;
+  const int nk = n * k;
   float* jbL = sm;
   float* YL = sm + nk * kLd;
   const int lane = threadIdx.x;
   for (int64_t t0 = (int64_t)blockIdx.x * kTile; t0 < T; t0 += (int64_t)gridDim.x * kTile) {
     __syncthreads();
-    stage_tile(t0, T, E, n, nk, jb, angle, torsion, idx_kj, pref, jbL, YL, kjL);
+    stage_tile<kTorsion>(t0, T, E, n, nk, jb, angle, torsion, idx_kj, pref, jbL, YL, kjL);
     for (int r = 0; r < kTile && t0 + r < T; ++r) {
-      for (int f = lane; f < nk; f += kTile) {
-        const int l = f / k;
-        aemb[(t0 + r) * nk + f] = jbL[f * kLd + r] * YL[l * l * kLd + r];
-      }
-      for (int f = lane; f < nnk; f += kTile) {
-        const int ab = f / k, q = f - ab * k;
-        temb[(t0 + r) * nnk + f] = jbL[((ab % n) * k + q) * kLd + r] * YL[ab * kLd + r];
+      for (int f = lane; f < nk; f += kTile)
+        aemb[(t0 + r) * nk + f] = jbL[f * kLd + r] * YL[y_row<kTorsion>(f / k) * kLd + r];
+      if constexpr (kTorsion) {
+        const int nnk = n * nk;
+        for (int f = lane; f < nnk; f += kTile) {
+          const int ab = f / k, q = f - ab * k;
+          temb[(t0 + r) * nnk + f] = jbL[((ab % n) * k + q) * kLd + r] * YL[ab * kLd + r];
+        }
       }
     }
   }
 }
 
 // Weight gradients: block b sums its contiguous range of tiles, thread = feature (angle
-// features first, then torsion features), blockIdx.y = chunk of kOC output columns; triplets
-// are added in index order.  One partial row [g_w1t | g_w2t] per block.
+// features first, then with kTorsion the torsion features), blockIdx.y = chunk of kOC output
+// columns; triplets are added in index order.  One partial row [g_w1t | g_w2t] per block.
+template <bool kTorsion>
 __global__ void triplet_proj_wgrad(
     int64_t T, int64_t E, int n, int k, int64_t tiles_per_block, const float* __restrict__ jb,
-    const float* __restrict__ angle, const float* __restrict__ torsion,
-    const int64_t* __restrict__ idx_kj, const float* __restrict__ pref,
-    const float* __restrict__ gS, int Oa, int oa_ld, int ba, const float* __restrict__ gP, int Ot,
-    int ot_ld, int bt, float* __restrict__ partials) {
+    const float* __restrict__ angle, const int64_t* __restrict__ idx_kj,
+    const float* __restrict__ pref, const float* __restrict__ gS, int Oa, int oa_ld, int ba,
+    float* __restrict__ partials, const float* __restrict__ torsion,
+    const float* __restrict__ gP, int Ot, int ot_ld, int bt) {
+  constexpr int kGroups = kTorsion ? 2 : 1;  // weight matrices
   extern __shared__ float sm[];
   __shared__ int64_t kjL[kTile];
-  __shared__ float gL[2][kTile][kOC];
-  const int nk = n * k, nnk = n * n * k;
+  __shared__ float gL[kGroups][kTile][kOC];
+  const int nk = n * k, nnk = kTorsion ? n * nk : 0;
   float* jbL = sm;
   float* YL = sm + nk * kLd;
   const int tid = threadIdx.x;
   const int o0 = blockIdx.y * kOC;
   const int f = tid;
-  const bool is_a = f < nk, is_t = f >= nk && f < nk + nnk;
+  const bool is_a = f < nk, is_t = kTorsion && f >= nk && f < nk + nnk;
   int jrow = 0, yrow = 0;
   if (is_a) {
-    jrow = f, yrow = (f / k) * (f / k);
+    jrow = f, yrow = y_row<kTorsion>(f / k);
   } else if (is_t) {
     const int ft = f - nk, ab = ft / k;
     jrow = (ab % n) * k + (ft - ab * k), yrow = ab;
   }
-  const int which = is_a ? 0 : 1;
-  const bool active = (is_a && o0 < Oa) || (is_t && o0 < Ot);
+  const int which = is_a ? 0 : kGroups - 1;
+  // blockIdx.y runs over the chunks of the wider weight group; a single group owns them all
+  const bool active = kTorsion ? (is_a && o0 < Oa) || (is_t && o0 < Ot) : is_a;
   float acc[kOC];
 #pragma unroll
   for (int u = 0; u < kOC; ++u) acc[u] = 0.f;
@@ -372,15 +421,15 @@ __global__ void triplet_proj_wgrad(
     const int64_t t0 = tile * kTile;
     if (t0 >= T) break;
     __syncthreads();
-    stage_tile(t0, T, E, n, nk, jb, angle, torsion, idx_kj, pref, jbL, YL, kjL);
-    for (int i = tid; i < 2 * kTile * kOC; i += blockDim.x) {
+    stage_tile<kTorsion>(t0, T, E, n, nk, jb, angle, torsion, idx_kj, pref, jbL, YL, kjL);
+    for (int i = tid; i < kGroups * kTile * kOC; i += blockDim.x) {
       const int w = i / (kTile * kOC), r = (i / kOC) % kTile, u = i % kOC;
       const int o = o0 + u;
       const int64_t t = t0 + r;
       float v = 0.f;
       if (t < T) {
-        if (w == 0 && o < Oa) v = gS[((int64_t)(o / ba) * T + t) * ba + o % ba];
-        if (w == 1 && o < Ot) v = gP[((int64_t)(o / bt) * T + t) * bt + o % bt];
+        if (w == 0 && o < Oa) v = gS[proj_index(o, t, T, ba)];
+        if (kTorsion && w == 1 && o < Ot) v = gP[proj_index(o, t, T, bt)];
       }
       gL[w][r][u] = v;
     }
@@ -395,7 +444,7 @@ __global__ void triplet_proj_wgrad(
   }
   const int64_t width = (int64_t)nk * oa_ld + (int64_t)nnk * ot_ld;
   float* row = partials + (int64_t)blockIdx.x * width;
-  if (is_a && o0 < oa_ld) {
+  if (is_a && (!kTorsion || o0 < oa_ld)) {
 #pragma unroll
     for (int u = 0; u < kOC; ++u) row[(int64_t)f * oa_ld + o0 + u] = acc[u];
   } else if (is_t && o0 < ot_ld) {
@@ -407,38 +456,39 @@ __global__ void triplet_proj_wgrad(
 
 // Geometry gradients: lane = triplet; g_emb[f] = sum_o w[f, o] g[o] is folded at once into
 // g_jb (per-triplet rows, summed per edge by the caller over the CSR of idx_kj) and g_Y, which
-// the harmonics' derivatives turn into g_angle and g_torsion.
+// the harmonics' derivatives turn into g_angle and, with kTorsion, g_torsion.
+template <bool kTorsion>
 __global__ __launch_bounds__(kTile) void triplet_proj_geom_bwd(
     int64_t T, int64_t E, int n, int k, const float* __restrict__ jb,
-    const float* __restrict__ angle,
-    const float* __restrict__ torsion, const int64_t* __restrict__ idx_kj,
+    const float* __restrict__ angle, const int64_t* __restrict__ idx_kj,
     const float* __restrict__ pref, const float* __restrict__ w1t, int Oa, int oa_ld, int ba,
-    const float* __restrict__ w2t, int Ot, int ot_ld, int bt, const float* __restrict__ gS,
-    const float* __restrict__ gP, float* __restrict__ g_jb_rows, float* __restrict__ g_angle,
-    float* __restrict__ g_torsion) {
+    const float* __restrict__ gS, float* __restrict__ g_jb_rows, float* __restrict__ g_angle,
+    const float* __restrict__ torsion, const float* __restrict__ w2t, int Ot, int ot_ld, int bt,
+    const float* __restrict__ gP, float* __restrict__ g_torsion) {
   extern __shared__ float sm[];
   __shared__ int64_t kjL[kTile];
-  const int nk = n * k, nn = n * n;
+  const int nk = n * k, ny = y_planes<kTorsion>(n);
   float* jbL = sm;
   float* YL = sm + nk * kLd;
-  float* gjL = YL + nn * kLd;
+  float* gjL = YL + ny * kLd;
   float* gyL = gjL + nk * kLd;
   const int lane = threadIdx.x;
   for (int64_t t0 = (int64_t)blockIdx.x * kTile; t0 < T; t0 += (int64_t)gridDim.x * kTile) {
     __syncthreads();
-    stage_tile(t0, T, E, n, nk, jb, angle, torsion, idx_kj, pref, jbL, YL, kjL);
+    stage_tile<kTorsion>(t0, T, E, n, nk, jb, angle, torsion, idx_kj, pref, jbL, YL, kjL);
     const int64_t t = t0 + lane;
     for (int i = 0; i < nk; ++i) gjL[i * kLd + lane] = 0.f;
-    for (int i = 0; i < nn; ++i) gyL[i * kLd + lane] = 0.f;
+    for (int i = 0; i < ny; ++i) gyL[i * kLd + lane] = 0.f;
     for (int o0 = 0; o0 < Oa; o0 += kOC) {
       float g[kOC];
 #pragma unroll
       for (int u = 0; u < kOC; ++u) {
         const int o = o0 + u;
-        g[u] = (t < T && o < Oa) ? gS[((int64_t)(o / ba) * T + t) * ba + o % ba] : 0.f;
+        g[u] = (t < T && o < Oa) ? gS[proj_index(o, t, T, ba)] : 0.f;
       }
       for (int l = 0; l < n; ++l) {
-        const float y = YL[l * l * kLd + lane];
+        const int yl = y_row<kTorsion>(l);
+        const float y = YL[yl * kLd + lane];
         float gy = 0.f;
         for (int q = 0; q < k; ++q) {
           const int f = l * k + q;
@@ -449,36 +499,39 @@ __global__ __launch_bounds__(kTile) void triplet_proj_geom_bwd(
           gjL[f * kLd + lane] += ge * y;
           gy = fmaf(ge, jbL[f * kLd + lane], gy);
         }
-        gyL[l * l * kLd + lane] += gy;
+        gyL[yl * kLd + lane] += gy;
       }
     }
-    for (int o0 = 0; o0 < Ot; o0 += kOC) {
-      float g[kOC];
+    if constexpr (kTorsion) {
+      for (int o0 = 0; o0 < Ot; o0 += kOC) {
+        float g[kOC];
 #pragma unroll
-      for (int u = 0; u < kOC; ++u) {
-        const int o = o0 + u;
-        g[u] = (t < T && o < Ot) ? gP[((int64_t)(o / bt) * T + t) * bt + o % bt] : 0.f;
-      }
-      for (int ab = 0; ab < nn; ++ab) {
-        const float y = YL[ab * kLd + lane];
-        const int b = ab % n;
-        float gy = 0.f;
-        for (int q = 0; q < k; ++q) {
-          const float* w = w2t + ((int64_t)ab * k + q) * ot_ld + o0;
-          float ge = 0.f;
-#pragma unroll
-          for (int u = 0; u < kOC; ++u) ge = fmaf(w[u], g[u], ge);
-          gjL[(b * k + q) * kLd + lane] += ge * y;
-          gy = fmaf(ge, jbL[(b * k + q) * kLd + lane], gy);
+        for (int u = 0; u < kOC; ++u) {
+          const int o = o0 + u;
+          g[u] = (t < T && o < Ot) ? gP[proj_index(o, t, T, bt)] : 0.f;
         }
-        gyL[ab * kLd + lane] += gy;
+        for (int ab = 0; ab < ny; ++ab) {
+          const float y = YL[ab * kLd + lane];
+          const int b = ab % n;
+          float gy = 0.f;
+          for (int q = 0; q < k; ++q) {
+            const float* w = w2t + ((int64_t)ab * k + q) * ot_ld + o0;
+            float ge = 0.f;
+#pragma unroll
+            for (int u = 0; u < kOC; ++u) ge = fmaf(w[u], g[u], ge);
+            gjL[(b * k + q) * kLd + lane] += ge * y;
+            gy = fmaf(ge, jbL[(b * k + q) * kLd + lane], gy);
+          }
+          gyL[ab * kLd + lane] += gy;
+        }
       }
     }
     if (t < T) {
       float gt, gp;
-      sph_harmonics<true>(n, angle[t], torsion[t], pref, gyL + lane, kLd, &gt, &gp);
+      sph_harmonics<true, kTorsion>(n, angle[t], kTorsion ? torsion[t] : 0.f, pref, gyL + lane,
+                                    kLd, &gt, &gp);
       g_angle[t] = gt;
-      g_torsion[t] = gp;
+      if constexpr (kTorsion) g_torsion[t] = gp;
     }
     __syncthreads();
     for (int r = 0; r < kTile && t0 + r < T; ++r)
@@ -486,8 +539,10 @@ __global__ __launch_bounds__(kTile) void triplet_proj_geom_bwd(
   }
 }
 
+template <bool kTorsion>
 int64_t proj_bwd_blocks(int64_t T) {
-  return std::max<int64_t>(1, std::min<int64_t>(ceil_div(T, kTile), kProjBwdBlocks));
+  const int cap = kTorsion ? kProjBwdBlocks : kProjBwdBlocksAngleOnly;
+  return std::max<int64_t>(1, std::min<int64_t>(ceil_div(T, kTile), cap));
 }
 
 unsigned tile_grid(int64_t T) {
@@ -495,6 +550,132 @@ unsigned tile_grid(int64_t T) {
 }
 
 bool basis_ok(int n, int k) { return n >= 1 && k >= 1 && n <= 16 && k <= 64; }
+
+// dynamic LDS of one staged tile: the jb planes and the harmonics
+template <bool kTorsion>
+size_t tile_lds(int n, int k) {
+  return (size_t)(n * k + y_planes<kTorsion>(n)) * kLd * sizeof(float);
+}
+
+int64_t edge_basis_bwd_partial_rows(int64_t n_edges) {
+  return n_edges > 0 ? ceil_div(n_edges, kEdgeT) : 0;
+}
+
+template <bool kCut>
+int edge_basis_fwd_launch(const float* dist, int64_t n_edges, float cutoff, int envelope_exponent,
+                          const float* freq, int num_radial, const float* zeros,
+                          const float* norm, int num_spherical, float* rbf, float* jb,
+                          void* stream) {
+  GMP_CHECK_ARG(n_edges >= 0 && basis_ok(num_spherical, num_radial) && cutoff > 0.f &&
+                envelope_exponent >= 0);
+  if (n_edges == 0) return GMP_OK;
+  GMP_CHECK_ARG(dist && freq && zeros && norm && rbf && jb);
+  const int nk = num_spherical * num_radial;
+  const int64_t total = n_edges * (num_radial + nk);
+  GMP_CHECK_ARG(ceil_div(total, kEdgeT) <= INT32_MAX);
+  edge_basis_fwd<kCut><<<(unsigned)ceil_div(total, kEdgeT), kEdgeT, 0, as_stream(stream)>>>(
+      dist, n_edges, cutoff, envelope_exponent, freq, num_radial, zeros, norm, nk, rbf, jb);
+  return launch_status();
+}
+
+template <bool kCut>
+int edge_basis_bwd_launch(const float* dist, int64_t n_edges, float cutoff, int envelope_exponent,
+                          const float* freq, int num_radial, const float* zeros,
+                          const float* norm, int num_spherical, const float* grad_rbf,
+                          const float* grad_jb, float* grad_dist, float* grad_freq,
+                          float* freq_partials, void* stream) {
+  GMP_CHECK_ARG(n_edges >= 0 && basis_ok(num_spherical, num_radial) && cutoff > 0.f &&
+                envelope_exponent >= 0 && grad_freq);
+  if (n_edges == 0)
+    return hip_check(hipMemsetAsync(grad_freq, 0, num_radial * sizeof(float), as_stream(stream)));
+  GMP_CHECK_ARG(dist && freq && zeros && norm && grad_dist && freq_partials);
+  const int64_t nb = ceil_div(n_edges, kEdgeT);
+  GMP_CHECK_ARG(nb <= INT32_MAX);
+  edge_basis_bwd<kCut><<<(unsigned)nb, kEdgeT, 0, as_stream(stream)>>>(
+      dist, n_edges, cutoff, envelope_exponent, freq, num_radial, zeros, norm,
+      num_spherical * num_radial, grad_rbf, grad_jb, grad_dist, freq_partials);
+  int rc = launch_status();
+  if (rc != GMP_OK) return rc;
+  return gmp_sum_rows_f32(freq_partials, nb, num_radial, grad_freq, stream);
+}
+
+// The per-triplet launchers take SphereNet's argument lists; without kTorsion the torsion
+// arguments (torsion, w_t1_t, bt, P and their gradients) are null / 0 and not looked at.
+template <bool kTorsion>
+int triplet_proj_fwd_launch(int64_t n_triplets, int64_t n_edges, int n, int k, const float* jb,
+                            const float* angle, const float* torsion, const int64_t* idx_kj,
+                            const float* pref, const float* w_sbf1_t, int n_layers, int ba,
+                            const float* w_t1_t, int bt, float* S, float* P, void* stream) {
+  GMP_CHECK_ARG(n_triplets >= 0 && n_edges >= 0 && basis_ok(n, k) && n_layers >= 1 && ba >= 1 &&
+                (!kTorsion || bt >= 1));
+  if (n_triplets == 0) return GMP_OK;
+  GMP_CHECK_ARG(jb && angle && idx_kj && pref && w_sbf1_t && S && n_edges > 0 &&
+                (!kTorsion || (torsion && w_t1_t && P)));
+  const int Oa = n_layers * ba, Ot = n_layers * bt;
+  const int oa_ld = (int)ceil_div(Oa, kOC) * kOC, ot_ld = (int)ceil_div(Ot, kOC) * kOC;
+  const size_t lds = tile_lds<kTorsion>(n, k);
+  if (lds > kLdsCap) return GMP_ERR_UNSUPPORTED;
+  triplet_proj_fwd<kTorsion><<<tile_grid(n_triplets), kTile, lds, as_stream(stream)>>>(
+      n_triplets, n_edges, n, k, jb, angle, idx_kj, pref, w_sbf1_t, Oa, oa_ld, ba, S, torsion,
+      w_t1_t, Ot, ot_ld, bt, P);
+  return launch_status();
+}
+
+template <bool kTorsion>
+int triplet_emb_launch(int64_t n_triplets, int64_t n_edges, int n, int k, const float* jb,
+                       const float* angle, const float* torsion, const int64_t* idx_kj,
+                       const float* pref, float* angle_emb, float* torsion_emb, void* stream) {
+  GMP_CHECK_ARG(n_triplets >= 0 && n_edges >= 0 && basis_ok(n, k));
+  if (n_triplets == 0) return GMP_OK;
+  GMP_CHECK_ARG(jb && angle && idx_kj && pref && angle_emb && n_edges > 0 &&
+                (!kTorsion || (torsion && torsion_emb)));
+  const size_t lds = tile_lds<kTorsion>(n, k);
+  if (lds > kLdsCap) return GMP_ERR_UNSUPPORTED;
+  triplet_emb<kTorsion><<<tile_grid(n_triplets), kTile, lds, as_stream(stream)>>>(
+      n_triplets, n_edges, n, k, jb, angle, idx_kj, pref, angle_emb, torsion, torsion_emb);
+  return launch_status();
+}
+
+template <bool kTorsion>
+int triplet_proj_bwd_launch(int64_t n_triplets, int64_t n_edges, int n, int k, const float* jb,
+                            const float* angle, const float* torsion, const int64_t* idx_kj,
+                            const float* pref, const float* w_sbf1_t, int n_layers, int ba,
+                            const float* w_t1_t, int bt, const float* grad_S, const float* grad_P,
+                            float* grad_w, float* partials, float* grad_jb_rows,
+                            float* grad_angle, float* grad_torsion, void* stream) {
+  GMP_CHECK_ARG(n_triplets >= 0 && n_edges >= 0 && basis_ok(n, k) && n_layers >= 1 && ba >= 1 &&
+                (!kTorsion || bt >= 1) && grad_w);
+  const int nk = n * k, nnk = kTorsion ? n * nk : 0;
+  const int Oa = n_layers * ba, Ot = n_layers * bt;
+  const int oa_ld = (int)ceil_div(Oa, kOC) * kOC, ot_ld = (int)ceil_div(Ot, kOC) * kOC;
+  const int64_t width = (int64_t)nk * oa_ld + (int64_t)nnk * ot_ld;
+  hipStream_t s = as_stream(stream);
+  if (n_triplets == 0) return hip_check(hipMemsetAsync(grad_w, 0, width * sizeof(float), s));
+  GMP_CHECK_ARG(jb && angle && idx_kj && pref && w_sbf1_t && grad_S && partials && n_edges > 0 &&
+                (!kTorsion || (torsion && w_t1_t && grad_P)));
+  const int threads = (int)ceil_div(nk + nnk, kWave) * kWave;
+  const size_t lds = tile_lds<kTorsion>(n, k);
+  if (threads > 1024 || lds > kLdsCap) return GMP_ERR_UNSUPPORTED;
+  const int64_t nb = proj_bwd_blocks<kTorsion>(n_triplets);
+  const int64_t tpb = ceil_div(ceil_div(n_triplets, kTile), nb);
+  const int chunks = std::max(oa_ld, ot_ld) / kOC;
+  triplet_proj_wgrad<kTorsion><<<dim3((unsigned)nb, (unsigned)chunks), threads, lds, s>>>(
+      n_triplets, n_edges, n, k, tpb, jb, angle, idx_kj, pref, grad_S, Oa, oa_ld, ba, partials,
+      torsion, grad_P, Ot, ot_ld, bt);
+  int rc = launch_status();
+  if (rc != GMP_OK) return rc;
+  rc = gmp_sum_rows_f32(partials, nb, width, grad_w, stream);
+  if (rc != GMP_OK) return rc;
+  if (grad_jb_rows || grad_angle || (kTorsion && grad_torsion)) {
+    GMP_CHECK_ARG(grad_jb_rows && grad_angle && (!kTorsion || grad_torsion));
+    if (2 * lds > kLdsCap) return GMP_ERR_UNSUPPORTED;
+    triplet_proj_geom_bwd<kTorsion><<<tile_grid(n_triplets), kTile, 2 * lds, s>>>(
+        n_triplets, n_edges, n, k, jb, angle, idx_kj, pref, w_sbf1_t, Oa, oa_ld, ba, grad_S,
+        grad_jb_rows, grad_angle, torsion, w_t1_t, Ot, ot_ld, bt, grad_P, grad_torsion);
+    rc = launch_status();
+  }
+  return rc;
+}
 
 }  // namespace
 }  // namespace gmp
@@ -504,23 +685,27 @@ using namespace gmp;
 extern "C" {
 
 int64_t gmp_sph_edge_basis_bwd_partial_rows(int64_t n_edges) {
-  return n_edges > 0 ? ceil_div(n_edges, kEdgeT) : 0;
+  return edge_basis_bwd_partial_rows(n_edges);
+}
+
+int64_t gmp_dime_edge_basis_bwd_partial_rows(int64_t n_edges) {
+  return edge_basis_bwd_partial_rows(n_edges);
 }
 
 int gmp_sph_edge_basis_fwd_f32(const float* dist, int64_t n_edges, float cutoff,
                                int envelope_exponent, const float* freq, int num_radial,
                                const float* zeros, const float* norm, int num_spherical,
                                float* rbf, float* jb, void* stream) {
-  GMP_CHECK_ARG(n_edges >= 0 && basis_ok(num_spherical, num_radial) && cutoff > 0.f &&
-                envelope_exponent >= 0);
-  if (n_edges == 0) return GMP_OK;
-  GMP_CHECK_ARG(dist && freq && zeros && norm && rbf && jb);
-  const int nk = num_spherical * num_radial;
-  const int64_t total = n_edges * (num_radial + nk);
-  GMP_CHECK_ARG(ceil_div(total, kEdgeT) <= INT32_MAX);
-  edge_basis_fwd<<<(unsigned)ceil_div(total, kEdgeT), kEdgeT, 0, as_stream(stream)>>>(
-      dist, n_edges, cutoff, envelope_exponent, freq, num_radial, zeros, norm, nk, rbf, jb);
-  return launch_status();
+  return edge_basis_fwd_launch<false>(dist, n_edges, cutoff, envelope_exponent, freq, num_radial,
+                                      zeros, norm, num_spherical, rbf, jb, stream);
+}
+
+int gmp_dime_edge_basis_fwd_f32(const float* dist, int64_t n_edges, float cutoff,
+                                int envelope_exponent, const float* freq, int num_radial,
+                                const float* zeros, const float* norm, int num_spherical,
+                                float* rbf, float* sbe, void* stream) {
+  return edge_basis_fwd_launch<true>(dist, n_edges, cutoff, envelope_exponent, freq, num_radial,
+                                     zeros, norm, num_spherical, rbf, sbe, stream);
 }
 
 int gmp_sph_edge_basis_bwd_f32(const float* dist, int64_t n_edges, float cutoff,
@@ -528,19 +713,19 @@ int gmp_sph_edge_basis_bwd_f32(const float* dist, int64_t n_edges, float cutoff,
                                const float* zeros, const float* norm, int num_spherical,
                                const float* grad_rbf, const float* grad_jb, float* grad_dist,
                                float* grad_freq, float* freq_partials, void* stream) {
-  GMP_CHECK_ARG(n_edges >= 0 && basis_ok(num_spherical, num_radial) && cutoff > 0.f &&
-                envelope_exponent >= 0 && grad_freq);
-  if (n_edges == 0)
-    return hip_check(hipMemsetAsync(grad_freq, 0, num_radial * sizeof(float), as_stream(stream)));
-  GMP_CHECK_ARG(dist && freq && zeros && norm && grad_dist && freq_partials);
-  const int64_t nb = ceil_div(n_edges, kEdgeT);
-  GMP_CHECK_ARG(nb <= INT32_MAX);
-  edge_basis_bwd<<<(unsigned)nb, kEdgeT, 0, as_stream(stream)>>>(
-      dist, n_edges, cutoff, envelope_exponent, freq, num_radial, zeros, norm,
-      num_spherical * num_radial, grad_rbf, grad_jb, grad_dist, freq_partials);
-  int rc = launch_status();
-  if (rc != GMP_OK) return rc;
-  return gmp_sum_rows_f32(freq_partials, nb, num_radial, grad_freq, stream);
+  return edge_basis_bwd_launch<false>(dist, n_edges, cutoff, envelope_exponent, freq, num_radial,
+                                      zeros, norm, num_spherical, grad_rbf, grad_jb, grad_dist,
+                                      grad_freq, freq_partials, stream);
+}
+
+int gmp_dime_edge_basis_bwd_f32(const float* dist, int64_t n_edges, float cutoff,
+                                int envelope_exponent, const float* freq, int num_radial,
+                                const float* zeros, const float* norm, int num_spherical,
+                                const float* grad_rbf, const float* grad_sbe, float* grad_dist,
+                                float* grad_freq, float* freq_partials, void* stream) {
+  return edge_basis_bwd_launch<true>(dist, n_edges, cutoff, envelope_exponent, freq, num_radial,
+                                     zeros, norm, num_spherical, grad_rbf, grad_sbe, grad_dist,
+                                     grad_freq, freq_partials, stream);
 }
 
 int gmp_sph_triplet_proj_fwd_f32(int64_t n_triplets, int64_t n_edges, int num_spherical,
@@ -548,42 +733,41 @@ int gmp_sph_triplet_proj_fwd_f32(int64_t n_triplets, int64_t n_edges, int num_sp
                                  const float* torsion, const int64_t* idx_kj, const float* pref,
                                  const float* w_sbf1_t, int n_layers, int ba, const float* w_t1_t,
                                  int bt, float* S, float* P, void* stream) {
-  GMP_CHECK_ARG(n_triplets >= 0 && n_edges >= 0 && basis_ok(num_spherical, num_radial) &&
-                n_layers >= 1 && ba >= 1 && bt >= 1);
-  if (n_triplets == 0) return GMP_OK;
-  GMP_CHECK_ARG(jb && angle && torsion && idx_kj && pref && w_sbf1_t && w_t1_t && S && P &&
-                n_edges > 0);
-  const int Oa = n_layers * ba, Ot = n_layers * bt;
-  const int oa_ld = (int)ceil_div(Oa, kOC) * kOC, ot_ld = (int)ceil_div(Ot, kOC) * kOC;
-  const size_t lds = (size_t)(num_spherical * num_radial + num_spherical * num_spherical) * kLd *
-                     sizeof(float);
-  if (lds > 60 * 1024) return GMP_ERR_UNSUPPORTED;
-  triplet_proj_fwd<<<tile_grid(n_triplets), kTile, lds, as_stream(stream)>>>(
-      n_triplets, n_edges, num_spherical, num_radial, jb, angle, torsion, idx_kj, pref, w_sbf1_t,
-      Oa,
-      oa_ld, ba, w_t1_t, Ot, ot_ld, bt, S, P);
-  return launch_status();
+  return triplet_proj_fwd_launch<true>(n_triplets, n_edges, num_spherical, num_radial, jb, angle,
+                                       torsion, idx_kj, pref, w_sbf1_t, n_layers, ba, w_t1_t, bt,
+                                       S, P, stream);
+}
+
+int gmp_dime_triplet_proj_fwd_f32(int64_t n_triplets, int64_t n_edges, int num_spherical,
+                                  int num_radial, const float* sbe, const float* angle,
+                                  const int64_t* idx_kj, const float* pref, const float* w_sbf1_t,
+                                  int n_layers, int b, float* S, void* stream) {
+  return triplet_proj_fwd_launch<false>(n_triplets, n_edges, num_spherical, num_radial, sbe, angle,
+                                        nullptr, idx_kj, pref, w_sbf1_t, n_layers, b, nullptr, 0,
+                                        S, nullptr, stream);
 }
 
 int gmp_sph_triplet_emb_f32(int64_t n_triplets, int64_t n_edges, int num_spherical,
                             int num_radial, const float* jb, const float* angle,
                             const float* torsion, const int64_t* idx_kj, const float* pref,
                             float* angle_emb, float* torsion_emb, void* stream) {
-  GMP_CHECK_ARG(n_triplets >= 0 && n_edges >= 0 && basis_ok(num_spherical, num_radial));
-  if (n_triplets == 0) return GMP_OK;
-  GMP_CHECK_ARG(jb && angle && torsion && idx_kj && pref && angle_emb && torsion_emb &&
-                n_edges > 0);
-  const size_t lds = (size_t)(num_spherical * num_radial + num_spherical * num_spherical) * kLd *
-                     sizeof(float);
-  if (lds > 60 * 1024) return GMP_ERR_UNSUPPORTED;
-  triplet_emb<<<tile_grid(n_triplets), kTile, lds, as_stream(stream)>>>(
-      n_triplets, n_edges, num_spherical, num_radial, jb, angle, torsion, idx_kj, pref, angle_emb,
-      torsion_emb);
-  return launch_status();
+  return triplet_emb_launch<true>(n_triplets, n_edges, num_spherical, num_radial, jb, angle,
+                                  torsion, idx_kj, pref, angle_emb, torsion_emb, stream);
+}
+
+int gmp_dime_triplet_emb_f32(int64_t n_triplets, int64_t n_edges, int num_spherical,
+                             int num_radial, const float* sbe, const float* angle,
+                             const int64_t* idx_kj, const float* pref, float* sbf, void* stream) {
+  return triplet_emb_launch<false>(n_triplets, n_edges, num_spherical, num_radial, sbe, angle,
+                                   nullptr, idx_kj, pref, sbf, nullptr, stream);
 }
 
 int64_t gmp_sph_triplet_proj_bwd_partial_rows(int64_t n_triplets) {
-  return proj_bwd_blocks(n_triplets);
+  return proj_bwd_blocks<true>(n_triplets);
+}
+
+int64_t gmp_dime_triplet_proj_bwd_partial_rows(int64_t n_triplets) {
+  return proj_bwd_blocks<false>(n_triplets);
 }
 
 int gmp_sph_triplet_proj_bwd_f32(int64_t n_triplets, int64_t n_edges, int num_spherical,
@@ -593,39 +777,22 @@ int gmp_sph_triplet_proj_bwd_f32(int64_t n_triplets, int64_t n_edges, int num_sp
                                  int bt, const float* grad_S, const float* grad_P,
                                  float* grad_w, float* partials, float* grad_jb_rows,
                                  float* grad_angle, float* grad_torsion, void* stream) {
-  GMP_CHECK_ARG(n_triplets >= 0 && n_edges >= 0 && basis_ok(num_spherical, num_radial) &&
-                n_layers >= 1 && ba >= 1 && bt >= 1 && grad_w);
-  const int n = num_spherical, k = num_radial, nk = n * k, nnk = n * n * k;
-  const int Oa = n_layers * ba, Ot = n_layers * bt;
-  const int oa_ld = (int)ceil_div(Oa, kOC) * kOC, ot_ld = (int)ceil_div(Ot, kOC) * kOC;
-  const int64_t width = (int64_t)nk * oa_ld + (int64_t)nnk * ot_ld;
-  hipStream_t s = as_stream(stream);
-  if (n_triplets == 0) return hip_check(hipMemsetAsync(grad_w, 0, width * sizeof(float), s));
-  GMP_CHECK_ARG(jb && angle && torsion && idx_kj && pref && w_sbf1_t && w_t1_t && grad_S &&
-                grad_P && partials && n_edges > 0);
-  const int feats = nk + nnk;
-  const int threads = (int)ceil_div(feats, kWave) * kWave;
-  const size_t lds = (size_t)(nk + n * n) * kLd * sizeof(float);
-  if (threads > 1024 || lds > 60 * 1024) return GMP_ERR_UNSUPPORTED;
-  const int64_t nb = proj_bwd_blocks(n_triplets);
-  const int64_t tpb = ceil_div(ceil_div(n_triplets, kTile), nb);
-  const int chunks = std::max(oa_ld, ot_ld) / kOC;
-  triplet_proj_wgrad<<<dim3((unsigned)nb, (unsigned)chunks), threads, lds, s>>>(
-      n_triplets, n_edges, n, k, tpb, jb, angle, torsion, idx_kj, pref, grad_S, Oa, oa_ld, ba,
-      grad_P, Ot, ot_ld, bt, partials);
-  int rc = launch_status();
-  if (rc != GMP_OK) return rc;
-  rc = gmp_sum_rows_f32(partials, nb, width, grad_w, stream);
-  if (rc != GMP_OK) return rc;
-  if (grad_jb_rows || grad_angle || grad_torsion) {
-    GMP_CHECK_ARG(grad_jb_rows && grad_angle && grad_torsion);
-    if (2 * lds > 60 * 1024) return GMP_ERR_UNSUPPORTED;
-    triplet_proj_geom_bwd<<<tile_grid(n_triplets), kTile, 2 * lds, s>>>(
-        n_triplets, n_edges, n, k, jb, angle, torsion, idx_kj, pref, w_sbf1_t, Oa, oa_ld, ba,
-        w_t1_t, Ot, ot_ld, bt, grad_S, grad_P, grad_jb_rows, grad_angle, grad_torsion);
-    rc = launch_status();
-  }
-  return rc;
+  return triplet_proj_bwd_launch<true>(n_triplets, n_edges, num_spherical, num_radial, jb, angle,
+                                       torsion, idx_kj, pref, w_sbf1_t, n_layers, ba, w_t1_t, bt,
+                                       grad_S, grad_P, grad_w, partials, grad_jb_rows, grad_angle,
+                                       grad_torsion, stream);
+}
+
+int gmp_dime_triplet_proj_bwd_f32(int64_t n_triplets, int64_t n_edges, int num_spherical,
+                                  int num_radial, const float* sbe, const float* angle,
+                                  const int64_t* idx_kj, const float* pref, const float* w_sbf1_t,
+                                  int n_layers, int b, const float* grad_S, float* grad_w,
+                                  float* partials, float* grad_sbe_rows, float* grad_angle,
+                                  void* stream) {
+  return triplet_proj_bwd_launch<false>(n_triplets, n_edges, num_spherical, num_radial, sbe, angle,
+                                        nullptr, idx_kj, pref, w_sbf1_t, n_layers, b, nullptr, 0,
+                                        grad_S, nullptr, grad_w, partials, grad_sbe_rows,
+                                        grad_angle, nullptr, stream);
 }
 
 }  // extern "C"

@@ -1698,23 +1698,60 @@ void sph_tables(const Tensor& zeros, const Tensor& norm, int64_t* n, int64_t* k)
   *k = zeros.size(1);
 }
 
-std::tuple<Tensor, Tensor> sph_edge_basis_fwd(const Tensor& dist, const Tensor& freq,
-                                              const Tensor& zeros, const Tensor& norm,
-                                              double cutoff, int64_t envelope_exponent) {
-  OpGuard g(dist, "sph_edge_basis_fwd");
+// K18 / K18d per edge: the two families differ in the C entry point only
+std::string c_name(const char* op) { return std::string("gmp_") + op + "_f32"; }
+
+std::tuple<Tensor, Tensor> edge_basis_fwd(decltype(&gmp_sph_edge_basis_fwd_f32) entry,
+                                          const char* op, const Tensor& dist, const Tensor& freq,
+                                          const Tensor& zeros, const Tensor& norm, double cutoff,
+                                          int64_t envelope_exponent) {
+  OpGuard g(dist, op);
   f32(dist, "dist");
   f32(freq, "freq");
   int64_t n, k;
   sph_tables(zeros, norm, &n, &k);
-  TORCH_CHECK(dist.dim() == 1, "gmp.sph_edge_basis_fwd: dist (E)");
+  TORCH_CHECK(dist.dim() == 1, "gmp.", op, ": dist (E)");
   numel(freq, k, "freq");
   const int64_t E = dist.numel();
   Tensor rbf = at::empty({E, k}, dist.options()), jb = at::empty({E, n * k}, dist.options());
-  check_rc(gmp_sph_edge_basis_fwd_f32(fp(dist), E, (float)cutoff, (int)envelope_exponent,
-                                      fp(freq), (int)k, fp(zeros), fp(norm), (int)n, fp(rbf),
-                                      fp(jb), cur_stream()),
-           "gmp_sph_edge_basis_fwd_f32");
+  check_rc(entry(fp(dist), E, (float)cutoff, (int)envelope_exponent, fp(freq), (int)k, fp(zeros),
+                 fp(norm), (int)n, fp(rbf), fp(jb), cur_stream()),
+           c_name(op).c_str());
   return {rbf, jb};
+}
+
+std::tuple<Tensor, Tensor> edge_basis_bwd(decltype(&gmp_sph_edge_basis_bwd_f32) entry,
+                                          int64_t (*partial_rows)(int64_t), const char* op,
+                                          const char* grad_jb_name, const Tensor& dist,
+                                          const Tensor& freq, const Tensor& zeros,
+                                          const Tensor& norm, double cutoff,
+                                          int64_t envelope_exponent,
+                                          const optional<Tensor>& grad_rbf,
+                                          const optional<Tensor>& grad_jb) {
+  OpGuard g(dist, op);
+  f32(dist, "dist");
+  f32(freq, "freq");
+  int64_t n, k;
+  sph_tables(zeros, norm, &n, &k);
+  TORCH_CHECK(dist.dim() == 1, "gmp.", op, ": dist (E)");
+  numel(freq, k, "freq");
+  const int64_t E = dist.numel();
+  opt_f32(grad_rbf, {E, k}, "grad_rbf");
+  opt_f32(grad_jb, {E, n * k}, grad_jb_name);
+  Tensor gd = at::empty({E}, dist.options()), gf = at::empty({k}, dist.options());
+  Tensor part = at::empty({partial_rows(E), k}, dist.options());
+  check_rc(entry(fp(dist), E, (float)cutoff, (int)envelope_exponent, fp(freq), (int)k, fp(zeros),
+                 fp(norm), (int)n, cfp(grad_rbf), cfp(grad_jb), fp(gd), fp(gf), fp(part),
+                 cur_stream()),
+           c_name(op).c_str());
+  return {gd, gf};
+}
+
+std::tuple<Tensor, Tensor> sph_edge_basis_fwd(const Tensor& dist, const Tensor& freq,
+                                              const Tensor& zeros, const Tensor& norm,
+                                              double cutoff, int64_t envelope_exponent) {
+  return edge_basis_fwd(gmp_sph_edge_basis_fwd_f32, "sph_edge_basis_fwd", dist, freq, zeros, norm,
+                        cutoff, envelope_exponent);
 }
 
 std::tuple<Tensor, Tensor> sph_edge_basis_bwd(const Tensor& dist, const Tensor& freq,
@@ -1722,24 +1759,9 @@ std::tuple<Tensor, Tensor> sph_edge_basis_bwd(const Tensor& dist, const Tensor& 
                                               double cutoff, int64_t envelope_exponent,
                                               const optional<Tensor>& grad_rbf,
                                               const optional<Tensor>& grad_jb) {
-  OpGuard g(dist, "sph_edge_basis_bwd");
-  f32(dist, "dist");
-  f32(freq, "freq");
-  int64_t n, k;
-  sph_tables(zeros, norm, &n, &k);
-  TORCH_CHECK(dist.dim() == 1, "gmp.sph_edge_basis_bwd: dist (E)");
-  numel(freq, k, "freq");
-  const int64_t E = dist.numel();
-  opt_f32(grad_rbf, {E, k}, "grad_rbf");
-  opt_f32(grad_jb, {E, n * k}, "grad_jb");
-  Tensor gd = at::empty({E}, dist.options()), gf = at::empty({k}, dist.options());
-  Tensor part = at::empty({gmp_sph_edge_basis_bwd_partial_rows(E), k}, dist.options());
-  check_rc(gmp_sph_edge_basis_bwd_f32(fp(dist), E, (float)cutoff, (int)envelope_exponent,
-                                      fp(freq), (int)k, fp(zeros), fp(norm), (int)n,
-                                      cfp(grad_rbf), cfp(grad_jb), fp(gd), fp(gf), fp(part),
-                                      cur_stream()),
-           "gmp_sph_edge_basis_bwd_f32");
-  return {gd, gf};
+  return edge_basis_bwd(gmp_sph_edge_basis_bwd_f32, gmp_sph_edge_basis_bwd_partial_rows,
+                        "sph_edge_basis_bwd", "grad_jb", dist, freq, zeros, norm, cutoff,
+                        envelope_exponent, grad_rbf, grad_jb);
 }
 
 // shared argument checks of the per-triplet K18 entry points; returns T
@@ -1837,29 +1859,52 @@ void interact_args(const Tensor& S, const Tensor& P, const Tensor& wa, const Ten
               "gmp: S (T, ba), P (T, bt), w_sbf2 (I, ba), w_t2 (I, bt)");
 }
 
+// The checks that the forwards of K19 and K19d share, for T triplets and I channels (S and the
+// weights are checked before): src (n_src, I), gather_idx (T), perm (T) or none, rowptr
+// (n_seg + 1).  Returns perm's data or null.
+const int64_t* interact_fwd_args(const char* op, const Tensor& src, int64_t T, int64_t I,
+                                 const Tensor& gidx, const optional<Tensor>& perm,
+                                 const Tensor& rowptr) {
+  f32(src, "src");
+  i64(gidx, "gather_idx");
+  i64(rowptr, "rowptr");
+  TORCH_CHECK(src.dim() == 2 && src.size(1) == I, "gmp.", op, ": src (n_src, I)");
+  numel(gidx, T, "gather_idx");
+  TORCH_CHECK(rowptr.numel() >= 1, "gmp.", op, ": rowptr (n_seg + 1)");
+  if (!perm.has_value() || !perm->defined()) return nullptr;
+  i64(*perm, "perm");
+  numel(*perm, T, "perm");
+  return ip(*perm);
+}
+
+// The same for the two backwards: grad_m (E, I), xd (E, I), idx_kj (T), offsets (E + 1).
+// Returns E.
+int64_t interact_bwd_args(const char* op, const Tensor& gm, const Tensor& xd, int64_t T, int64_t I,
+                          const Tensor& idx_kj, const Tensor& offs) {
+  f32(gm, "grad_m");
+  f32(xd, "xd");
+  i64(idx_kj, "idx_kj");
+  i64(offs, "offsets");
+  TORCH_CHECK(xd.dim() == 2 && xd.size(1) == I, "gmp.", op, ": xd (E, I)");
+  const int64_t E = xd.size(0);
+  shape(gm, {E, I}, "grad_m");
+  numel(idx_kj, T, "idx_kj");
+  numel(offs, E + 1, "offsets");
+  return E;
+}
+
 Tensor triplet_interact_fwd(const Tensor& src, const Tensor& S, const Tensor& P, const Tensor& wa,
                             const Tensor& wt, const Tensor& gidx, const optional<Tensor>& perm,
                             const Tensor& rowptr) {
   OpGuard g(src, "triplet_interact_fwd");
-  f32(src, "src");
   interact_args(S, P, wa, wt);
-  i64(gidx, "gather_idx");
-  i64(rowptr, "rowptr");
   const int64_t T = S.size(0), I = wa.size(0);
-  TORCH_CHECK(src.dim() == 2 && src.size(1) == I, "gmp.triplet_interact_fwd: src (n_src, I)");
-  numel(gidx, T, "gather_idx");
-  TORCH_CHECK(rowptr.numel() >= 1, "gmp.triplet_interact_fwd: rowptr (n_seg + 1)");
-  const bool hp = perm.has_value() && perm->defined();
-  if (hp) {
-    i64(*perm, "perm");
-    numel(*perm, T, "perm");
-  }
+  const int64_t* pp = interact_fwd_args("triplet_interact_fwd", src, T, I, gidx, perm, rowptr);
   const int64_t n_seg = rowptr.numel() - 1;
   Tensor out = at::empty({n_seg, I}, src.options());
   check_rc(gmp_triplet_interact_fwd_f32(n_seg, src.size(0), T, I, (int)S.size(1), (int)P.size(1),
-                                        fp(src), fp(S), fp(P), fp(wa), fp(wt), ip(gidx),
-                                        hp ? ip(*perm) : nullptr, ip(rowptr), fp(out),
-                                        cur_stream()),
+                                        fp(src), fp(S), fp(P), fp(wa), fp(wt), ip(gidx), pp,
+                                        ip(rowptr), fp(out), cur_stream()),
            "gmp_triplet_interact_fwd_f32");
   return out;
 }
@@ -1868,17 +1913,9 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> triplet_interact_bwd(
     const Tensor& gm, const Tensor& xd, const Tensor& S, const Tensor& P, const Tensor& wa,
     const Tensor& wt, const Tensor& idx_kj, const Tensor& offs) {
   OpGuard g(gm, "triplet_interact_bwd");
-  f32(gm, "grad_m");
-  f32(xd, "xd");
   interact_args(S, P, wa, wt);
-  i64(idx_kj, "idx_kj");
-  i64(offs, "offsets");
   const int64_t T = S.size(0), I = wa.size(0), ba = S.size(1), bt = P.size(1);
-  TORCH_CHECK(xd.dim() == 2 && xd.size(1) == I, "gmp.triplet_interact_bwd: xd (E, I)");
-  const int64_t E = xd.size(0);
-  shape(gm, {E, I}, "grad_m");
-  numel(idx_kj, T, "idx_kj");
-  numel(offs, E + 1, "offsets");
+  const int64_t E = interact_bwd_args("triplet_interact_bwd", gm, xd, T, I, idx_kj, offs);
   TORCH_CHECK(ba <= 16 && bt <= 16, "gmp.triplet_interact_bwd: basis_emb sizes <= 16");
   auto o = gm.options();
   Tensor gS = at::empty({T, ba}, o), gP = at::empty({T, bt}, o);
@@ -1895,20 +1932,8 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> triplet_interact_bwd(
 std::tuple<Tensor, Tensor> dime_edge_basis_fwd(const Tensor& dist, const Tensor& freq,
                                                const Tensor& zeros, const Tensor& norm,
                                                double cutoff, int64_t envelope_exponent) {
-  OpGuard g(dist, "dime_edge_basis_fwd");
-  f32(dist, "dist");
-  f32(freq, "freq");
-  int64_t n, k;
-  sph_tables(zeros, norm, &n, &k);
-  TORCH_CHECK(dist.dim() == 1, "gmp.dime_edge_basis_fwd: dist (E)");
-  numel(freq, k, "freq");
-  const int64_t E = dist.numel();
-  Tensor rbf = at::empty({E, k}, dist.options()), sbe = at::empty({E, n * k}, dist.options());
-  check_rc(gmp_dime_edge_basis_fwd_f32(fp(dist), E, (float)cutoff, (int)envelope_exponent,
-                                       fp(freq), (int)k, fp(zeros), fp(norm), (int)n, fp(rbf),
-                                       fp(sbe), cur_stream()),
-           "gmp_dime_edge_basis_fwd_f32");
-  return {rbf, sbe};
+  return edge_basis_fwd(gmp_dime_edge_basis_fwd_f32, "dime_edge_basis_fwd", dist, freq, zeros,
+                        norm, cutoff, envelope_exponent);
 }
 
 std::tuple<Tensor, Tensor> dime_edge_basis_bwd(const Tensor& dist, const Tensor& freq,
@@ -1916,24 +1941,9 @@ std::tuple<Tensor, Tensor> dime_edge_basis_bwd(const Tensor& dist, const Tensor&
                                                double cutoff, int64_t envelope_exponent,
                                                const optional<Tensor>& grad_rbf,
                                                const optional<Tensor>& grad_sbe) {
-  OpGuard g(dist, "dime_edge_basis_bwd");
-  f32(dist, "dist");
-  f32(freq, "freq");
-  int64_t n, k;
-  sph_tables(zeros, norm, &n, &k);
-  TORCH_CHECK(dist.dim() == 1, "gmp.dime_edge_basis_bwd: dist (E)");
-  numel(freq, k, "freq");
-  const int64_t E = dist.numel();
-  opt_f32(grad_rbf, {E, k}, "grad_rbf");
-  opt_f32(grad_sbe, {E, n * k}, "grad_sbe");
-  Tensor gd = at::empty({E}, dist.options()), gf = at::empty({k}, dist.options());
-  Tensor part = at::empty({gmp_dime_edge_basis_bwd_partial_rows(E), k}, dist.options());
-  check_rc(gmp_dime_edge_basis_bwd_f32(fp(dist), E, (float)cutoff, (int)envelope_exponent,
-                                       fp(freq), (int)k, fp(zeros), fp(norm), (int)n,
-                                       cfp(grad_rbf), cfp(grad_sbe), fp(gd), fp(gf), fp(part),
-                                       cur_stream()),
-           "gmp_dime_edge_basis_bwd_f32");
-  return {gd, gf};
+  return edge_basis_bwd(gmp_dime_edge_basis_bwd_f32, gmp_dime_edge_basis_bwd_partial_rows,
+                        "dime_edge_basis_bwd", "grad_sbe", dist, freq, zeros, norm, cutoff,
+                        envelope_exponent, grad_rbf, grad_sbe);
 }
 
 // shared argument checks of the per-triplet K18d entry points; returns T
@@ -2017,24 +2027,13 @@ Tensor triplet_interact1_fwd(const Tensor& src, const Tensor& S, const Tensor& w
                              const Tensor& gidx, const optional<Tensor>& perm,
                              const Tensor& rowptr) {
   OpGuard g(src, "triplet_interact1_fwd");
-  f32(src, "src");
   interact1_args(S, w);
-  i64(gidx, "gather_idx");
-  i64(rowptr, "rowptr");
   const int64_t T = S.size(0), I = w.size(0);
-  TORCH_CHECK(src.dim() == 2 && src.size(1) == I, "gmp.triplet_interact1_fwd: src (n_src, I)");
-  numel(gidx, T, "gather_idx");
-  TORCH_CHECK(rowptr.numel() >= 1, "gmp.triplet_interact1_fwd: rowptr (n_seg + 1)");
-  const bool hp = perm.has_value() && perm->defined();
-  if (hp) {
-    i64(*perm, "perm");
-    numel(*perm, T, "perm");
-  }
+  const int64_t* pp = interact_fwd_args("triplet_interact1_fwd", src, T, I, gidx, perm, rowptr);
   const int64_t n_seg = rowptr.numel() - 1;
   Tensor out = at::empty({n_seg, I}, src.options());
   check_rc(gmp_triplet_interact1_fwd_f32(n_seg, src.size(0), T, I, (int)S.size(1), fp(src), fp(S),
-                                         fp(w), ip(gidx), hp ? ip(*perm) : nullptr, ip(rowptr),
-                                         fp(out), cur_stream()),
+                                         fp(w), ip(gidx), pp, ip(rowptr), fp(out), cur_stream()),
            "gmp_triplet_interact1_fwd_f32");
   return out;
 }
@@ -2043,17 +2042,9 @@ std::tuple<Tensor, Tensor> triplet_interact1_bwd(const Tensor& gm, const Tensor&
                                                  const Tensor& S, const Tensor& w,
                                                  const Tensor& idx_kj, const Tensor& offs) {
   OpGuard g(gm, "triplet_interact1_bwd");
-  f32(gm, "grad_m");
-  f32(xd, "xd");
   interact1_args(S, w);
-  i64(idx_kj, "idx_kj");
-  i64(offs, "offsets");
   const int64_t T = S.size(0), I = w.size(0), b = S.size(1);
-  TORCH_CHECK(xd.dim() == 2 && xd.size(1) == I, "gmp.triplet_interact1_bwd: xd (E, I)");
-  const int64_t E = xd.size(0);
-  shape(gm, {E, I}, "grad_m");
-  numel(idx_kj, T, "idx_kj");
-  numel(offs, E + 1, "offsets");
+  const int64_t E = interact_bwd_args("triplet_interact1_bwd", gm, xd, T, I, idx_kj, offs);
   TORCH_CHECK(b <= 16, "gmp.triplet_interact1_bwd: basis_emb_size <= 16");
   auto o = gm.options();
   Tensor gS = at::empty({T, b}, o), gw = at::empty({I, b}, o);
@@ -2402,17 +2393,9 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> triplet_interact_bwd(
     const Tensor& wt, const Tensor&, const Tensor&) {
   return {at::empty_like(S), at::empty_like(P), at::empty_like(wa), at::empty_like(wt)};
 }
-std::tuple<Tensor, Tensor> dime_edge_basis_fwd(const Tensor& dist, const Tensor&,
-                                               const Tensor& zeros, const Tensor&, double,
-                                               int64_t) {
-  return {at::empty({dist.numel(), zeros.size(1)}, dist.options()),
-          at::empty({dist.numel(), zeros.numel()}, dist.options())};
-}
-std::tuple<Tensor, Tensor> dime_edge_basis_bwd(const Tensor& dist, const Tensor& freq,
-                                               const Tensor&, const Tensor&, double, int64_t,
-                                               const optional<Tensor>&, const optional<Tensor>&) {
-  return {at::empty_like(dist), at::empty_like(freq)};
-}
+// K18d's per-edge ops have K18's signatures and shapes
+constexpr auto& dime_edge_basis_fwd = sph_edge_basis_fwd;
+constexpr auto& dime_edge_basis_bwd = sph_edge_basis_bwd;
 Tensor dime_triplet_proj_fwd(const Tensor& sbe, const Tensor& angle, const Tensor&, const Tensor&,
                              const Tensor&, int64_t, int64_t, int64_t L, int64_t b) {
   return at::empty({L, angle.numel(), b}, sbe.options());

@@ -1425,28 +1425,40 @@ def _pad8(v):
     return (v + 7) // 8 * 8
 
 
-class SphEdgeBasisFn(torch.autograd.Function):
+def _edge_basis_fn(name, family, doc):
+    """The autograd Function over gmp.<family>_edge_basis_fwd / _bwd (K18 and K18d take the same
+    arguments and return the same shapes)."""
+
+    class Fn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, dist, freq, zeros, norm, cutoff, envelope_exponent):
+            dist, freq = _f32c(dist), _f32c(freq)
+            _need_cuda(dist, freq, zeros, norm)
+            ctx.save_for_backward(dist, freq, zeros, norm)
+            ctx.cutoff, ctx.p = float(cutoff), int(envelope_exponent)
+            fwd = getattr(_lib.torch_ops(), family + "_edge_basis_fwd")
+            return fwd(dist, freq, zeros, norm, ctx.cutoff, ctx.p)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, g_rbf, g_jb):
+            dist, freq, zeros, norm = ctx.saved_tensors
+            g_rbf = _f32c(g_rbf) if g_rbf is not None else None
+            g_jb = _f32c(g_jb) if g_jb is not None else None
+            bwd = getattr(_lib.torch_ops(), family + "_edge_basis_bwd")
+            gd, gf = bwd(dist, freq, zeros, norm, ctx.cutoff, ctx.p, g_rbf, g_jb)
+            return gd, gf, None, None, None, None
+
+    Fn.__name__ = Fn.__qualname__ = name
+    Fn.__doc__ = doc
+    return Fn
+
+
+SphEdgeBasisFn = _edge_basis_fn(
+    "SphEdgeBasisFn", "sph",
     """(rbf (E, k), jb (E, n k)) of K18 gmp_sph_edge_basis_*: the radial basis
     envelope(x) sin(freq x) and the normalised spherical Bessel values N_lq j_l(z_lq x),
-    x = dist / cutoff.  Gradients reach dist and freq."""
-
-    @staticmethod
-    def forward(ctx, dist, freq, zeros, norm, cutoff, envelope_exponent):
-        dist, freq = _f32c(dist), _f32c(freq)
-        _need_cuda(dist, freq, zeros, norm)
-        ctx.save_for_backward(dist, freq, zeros, norm)
-        ctx.cutoff, ctx.p = float(cutoff), int(envelope_exponent)
-        return _lib.torch_ops().sph_edge_basis_fwd(dist, freq, zeros, norm, ctx.cutoff, ctx.p)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g_rbf, g_jb):
-        dist, freq, zeros, norm = ctx.saved_tensors
-        g_rbf = _f32c(g_rbf) if g_rbf is not None else None
-        g_jb = _f32c(g_jb) if g_jb is not None else None
-        gd, gf = _lib.torch_ops().sph_edge_basis_bwd(dist, freq, zeros, norm, ctx.cutoff, ctx.p,
-                                                     g_rbf, g_jb)
-        return gd, gf, None, None, None, None
+    x = dist / cutoff.  Gradients reach dist and freq.""")
 
 
 def sph_feature_major(weights, width):
@@ -1517,6 +1529,18 @@ def sph_triplet_embeddings(jb, angle, torsion, idx_kj, pref, n, k):
                                             _i64c(idx_kj), pref, n, k)
 
 
+def _interact_grad_xd(ctx, interact_fwd, gm, xd, factors, idx_kj, idx_ji):
+    """grad_xd of K19 / K19d, where asked for: the forward kernel run over the CSR of idx_kj,
+    gathering grad_m by idx_ji.  `factors` are the forward's arguments between src and
+    gather_idx."""
+    if not ctx.needs_input_grad[0]:
+        return None
+    if idx_kj.numel() == 0 or xd.shape[0] == 0:
+        return torch.zeros_like(xd)
+    csr = get_csr(idx_kj, xd.shape[0])
+    return interact_fwd(gm, *factors, idx_ji, csr.perm, csr.rowptr)
+
+
 class TripletInteractFn(torch.autograd.Function):
     """K19 gmp_triplet_interact_*: m[e] = sum over the triplets t of edge e (the contiguous
     range [offsets[e], offsets[e+1]) that K11 emits) of xd[idx_kj[t]] * (W_sbf2 S_t) *
@@ -1537,39 +1561,17 @@ class TripletInteractFn(torch.autograd.Function):
         gm = _f32c(gm)
         tops = _lib.torch_ops()
         gS, gP, gWa, gWt = tops.triplet_interact_bwd(gm, xd, S, P, Wa, Wt, idx_kj, offsets)
-        gxd = None
-        if ctx.needs_input_grad[0]:
-            if idx_kj.numel() == 0 or xd.shape[0] == 0:
-                gxd = torch.zeros_like(xd)
-            else:
-                csr = get_csr(idx_kj, xd.shape[0])
-                gxd = tops.triplet_interact_fwd(gm, S, P, Wa, Wt, idx_ji, csr.perm, csr.rowptr)
+        gxd = _interact_grad_xd(ctx, tops.triplet_interact_fwd, gm, xd, (S, P, Wa, Wt), idx_kj,
+                                idx_ji)
         return gxd, gS, gP, gWa, gWt, None, None, None
 
 
 # ----------------------------------------------------------------------------------- DimeNet++
-class DimeEdgeBasisFn(torch.autograd.Function):
+DimeEdgeBasisFn = _edge_basis_fn(
+    "DimeEdgeBasisFn", "dime",
     """(rbf (E, k), sbe (E, n k)) of K18d gmp_dime_edge_basis_*: env(x) sin(freq x) and
     env(x) N_lq j_l(z_lq x), x = dist / cutoff, env the envelope cut to zero at and beyond the
-    cutoff (PyG's [x < 1]).  Gradients reach dist and freq."""
-
-    @staticmethod
-    def forward(ctx, dist, freq, zeros, norm, cutoff, envelope_exponent):
-        dist, freq = _f32c(dist), _f32c(freq)
-        _need_cuda(dist, freq, zeros, norm)
-        ctx.save_for_backward(dist, freq, zeros, norm)
-        ctx.cutoff, ctx.p = float(cutoff), int(envelope_exponent)
-        return _lib.torch_ops().dime_edge_basis_fwd(dist, freq, zeros, norm, ctx.cutoff, ctx.p)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g_rbf, g_sbe):
-        dist, freq, zeros, norm = ctx.saved_tensors
-        g_rbf = _f32c(g_rbf) if g_rbf is not None else None
-        g_sbe = _f32c(g_sbe) if g_sbe is not None else None
-        gd, gf = _lib.torch_ops().dime_edge_basis_bwd(dist, freq, zeros, norm, ctx.cutoff, ctx.p,
-                                                      g_rbf, g_sbe)
-        return gd, gf, None, None, None, None
+    cutoff (PyG's [x < 1]).  Gradients reach dist and freq.""")
 
 
 class DimeTripletProjFn(torch.autograd.Function):
@@ -1639,13 +1641,7 @@ class TripletInteract1Fn(torch.autograd.Function):
         gm = _f32c(gm)
         tops = _lib.torch_ops()
         gS, gW = tops.triplet_interact1_bwd(gm, xd, S, W, idx_kj, offsets)
-        gxd = None
-        if ctx.needs_input_grad[0]:
-            if idx_kj.numel() == 0 or xd.shape[0] == 0:
-                gxd = torch.zeros_like(xd)
-            else:
-                csr = get_csr(idx_kj, xd.shape[0])
-                gxd = tops.triplet_interact1_fwd(gm, S, W, idx_ji, csr.perm, csr.rowptr)
+        gxd = _interact_grad_xd(ctx, tops.triplet_interact1_fwd, gm, xd, (S, W), idx_kj, idx_ji)
         return gxd, gS, gW, None, None, None
 
 
