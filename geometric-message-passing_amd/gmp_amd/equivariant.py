@@ -391,7 +391,10 @@ class TPPlan:
         lmx = max(ir[0] for _, ir in tuple(irreps_in) + tuple(irreps_out) + tuple(irreps_sh))
         cg_floats = sum((2 * i["l1"] + 1) * (2 * i["l2"] + 1) * (2 * i["lo"] + 1)
                         for i in self.instructions)
-        if any(m != 1 for m, _ in irreps_sh) or sh_dim not in (1, 4, 9, 16, 25, 36) or \
+        # the z / dz kernels read SH component l2 * l2 + j (not Path.y_off): irreps_sh must be one
+        # irrep per l = 0..L in ascending order (any parities), as o3.sh_irreps(L) is
+        sh_ordered = [(m, ir[0]) for m, ir in irreps_sh] == [(1, l) for l in range(len(irreps_sh))]
+        if not sh_ordered or sh_dim not in (1, 4, 9, 16, 25, 36) or \
                 any(m > 128 for m, _ in irreps_in) or len(irreps_out) > 8 or lmx > 5 or \
                 len(self.instructions) > 48 or cg_floats > (8192 if lmx > 3 else 4096):
             raise NotImplementedError(f"TP {o3.irreps_str(irreps_in)} x {o3.irreps_str(irreps_sh)}"

@@ -537,7 +537,11 @@ int gmp_tp_edge_z_bwd_f32(const void* desc_host, const void* paths_dev, const fl
                           float* dx_edge, float* dY_edge, void* stream);
 /* Same with l_max = the largest l of any path (input, SH or output irreps; 0..3): with
  * l_max <= 2 the kernels are the l <= 2 instantiation (fewer registers, more waves per SIMD).
- * The plain entries above are l_max = 3 (any path). */
+ * The plain entries above are l_max = 3 (any path).  l_max 4 or 5, or sh_dim 25 or 36, select
+ * the runtime-l kernels.  A path whose l exceeds l_max is not computed: its z rows stay unwritten.
+ * SH layout contract: the kernels read SH component l2 * l2 + j of a path and ignore its y_off,
+ * so sh rows hold exactly one irrep per l = 0..L in ascending order (sh_dim = (L + 1)^2, any
+ * parities); gmp_amd.equivariant.TPPlan refuses any other irreps_sh.  dY_edge is (n_e, sh_dim). */
 int gmp_tp_edge_z_lmax_f32(const void* desc_host, int l_max, const void* paths_dev,
                            const float* cg_dev, int cg_len, const float* x, const float* sh,
                            const int64_t* src_sorted, const int64_t* perm, int64_t e0, int64_t e1,
