@@ -79,8 +79,9 @@ __device__ double ipow(double x, int n) {
   return r;
 }
 
-// envelope(x) = 1/x + a x^(p-1) + b x^p + c x^(p+1) and its derivative
-__device__ void env_eval(int exponent, double x, double* v, double* dv) {
+// envelope(x) = 1/x + a x^(p-1) + b x^p + c x^(p+1), its derivative and, where asked for, its
+// second derivative (a power whose coefficient is zero is not evaluated: p - 3 < 0 at p = 2)
+__device__ void env_eval(int exponent, double x, double* v, double* dv, double* d2v = nullptr) {
   const int p = exponent + 1;
   const double a = -(double)(p + 1) * (p + 2) / 2.0, b = (double)p * (p + 2),
                c = -(double)p * (p + 1) / 2.0;
@@ -89,6 +90,11 @@ __device__ void env_eval(int exponent, double x, double* v, double* dv) {
   *v = 1.0 / x + a * x0 + b * x1 + c * x2;
   const double xm = p >= 2 ? ipow(x, p - 2) : 0.0;
   *dv = -1.0 / (x * x) + a * (double)(p - 1) * xm + b * (double)p * x0 + c * (double)(p + 1) * x1;
+  if (d2v) {
+    const double xmm = p >= 3 ? ipow(x, p - 3) : 0.0;
+    *d2v = 2.0 / (x * x * x) + a * (double)((p - 1) * (p - 2)) * xmm +
+           b * (double)(p * (p - 1)) * xm + c * (double)((p + 1) * p) * x0;
+  }
 }
 
 // thread per (edge, column), columns [0, k) = rbf, [k, k + n k) = jb
@@ -171,6 +177,88 @@ __global__ __launch_bounds__(kEdgeT) void edge_basis_bwd(
     }
   }
   g_dist[e] = live ? (float)gd : 0.f;
+}
+
+// j_l''(y) = -(2 / y) j_l'(y) - (1 - l (l + 1) / y^2) j_l(y)  (the spherical Bessel equation)
+__device__ double sph_jl_second(int l, double y, double j, double dj) {
+  return -(2.0 / y) * dj - (1.0 - (double)(l * (l + 1)) / (y * y)) * j;
+}
+
+// Second backward of the edge basis: thread per edge.  The first backward maps (g_rbf, g_jb)
+// to (g_dist, g_freq); with the cotangents a_dist (E) and a_freq (k) of those this writes
+// gg_rbf, gg_jb (the gradients w.r.t. g_rbf, g_jb) and h_dist, and the block's h_freq partial
+// row, tree-summed in LDS in a fixed order as edge_basis_bwd.  With s = sin(f x), c = cos(f x):
+//   gg_rbf[q] = a_d (env' s + env f c) / cutoff + a_f[q] env x c
+//   gg_jb[lq] = a_d N (env' j + env z j') / cutoff            (kCut; N z j' / cutoff without)
+//   h_dist    = a_d [sum_q g_rbf (env'' s + 2 env' f c - env f^2 s)
+//                    + sum_lq g_jb N (env'' j + 2 env' z j' + env z^2 j'')] / cutoff^2
+//               + sum_q a_f[q] g_rbf (env' x c + env c - env f x s) / cutoff
+//   h_freq[q] = sum_e g_rbf [a_d (env' x c + env c - env f x s) / cutoff - a_f[q] env x^2 s]
+// All in double, rounded once.  With kCut a dead edge writes exact zeros everywhere.
+template <bool kCut>
+__global__ __launch_bounds__(kEdgeT) void edge_basis_bwd2(
+    const float* __restrict__ dist, int64_t E, float cutoff, int exponent,
+    const float* __restrict__ freq, int k, const float* __restrict__ zeros,
+    const float* __restrict__ norm, int nk, const float* __restrict__ g_rbf,
+    const float* __restrict__ g_jb, const float* __restrict__ a_dist,
+    const float* __restrict__ a_freq, float* __restrict__ gg_rbf, float* __restrict__ gg_jb,
+    float* __restrict__ h_dist, float* __restrict__ freq_partials) {
+  __shared__ float red[kEdgeT];
+  const int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const bool in_range = e < E;
+  const double xr = in_range ? (double)dist[e] / (double)cutoff : 1.0;
+  const bool live = in_range && (!kCut || xr < 1.0);
+  const double x = kCut && !live ? 0.5 : xr;
+  const double inv_c = 1.0 / (double)cutoff;
+  double env = 0.0, denv = 0.0, d2env = 0.0;
+  env_eval(exponent, x, &env, &denv, &d2env);
+  const double ad = (live && a_dist) ? (double)a_dist[e] : 0.0;
+  double hd = 0.0;
+  for (int q = 0; q < k; ++q) {
+    float contrib = 0.f, gg = 0.f;
+    if (live) {
+      const double f = (double)freq[q];
+      const double g = g_rbf ? (double)g_rbf[e * k + q] : 0.0;
+      const double af = a_freq ? (double)a_freq[q] : 0.0;
+      double s, c;
+      sincos(f * x, &s, &c);
+      const double m = denv * x * c + env * c - env * f * x * s;
+      gg = (float)(ad * (denv * s + env * f * c) * inv_c + af * env * x * c);
+      hd += ad * g * (d2env * s + 2.0 * denv * f * c - env * f * f * s) * inv_c * inv_c +
+            af * g * m * inv_c;
+      contrib = (float)(g * (ad * m * inv_c - af * env * x * x * s));
+    }
+    if (in_range) gg_rbf[e * k + q] = gg;
+    red[threadIdx.x] = contrib;
+    __syncthreads();
+    for (int w = kEdgeT / 2; w > 0; w >>= 1) {
+      if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) freq_partials[(int64_t)blockIdx.x * k + q] = red[0];
+    __syncthreads();
+  }
+  if (!in_range) return;
+  for (int lq = 0; lq < nk; ++lq) {
+    float gg = 0.f;
+    if (live) {
+      const double z = (double)zeros[lq], N = (double)norm[lq];
+      const int l = lq / k;
+      const double y = z * x;
+      const double j = sph_jl(l, y), dj = sph_jl_prime(l, y);
+      const double d2j = sph_jl_second(l, y, j, dj);
+      const double g = g_jb ? (double)g_jb[e * nk + lq] : 0.0;
+      if constexpr (kCut) {
+        gg = (float)(ad * N * (denv * j + env * z * dj) * inv_c);
+        hd += ad * g * N * (d2env * j + 2.0 * denv * z * dj + env * z * z * d2j) * inv_c * inv_c;
+      } else {
+        gg = (float)(ad * N * z * dj * inv_c);
+        hd += ad * g * N * z * z * d2j * inv_c * inv_c;
+      }
+    }
+    gg_jb[e * nk + lq] = gg;
+  }
+  h_dist[e] = live ? (float)hd : 0.f;
 }
 
 // the staged harmonics: row of Y_l0, and the number of rows
@@ -539,6 +627,252 @@ __global__ __launch_bounds__(kTile) void triplet_proj_geom_bwd(
   }
 }
 
+// ---- second backward of the angle-only projection (DimeNet++ energy-and-force training).
+// The first backward maps gS to (g_w, g_sbe, g_angle); with their cotangents a_w (feature-major
+// as w1t), a_sbe (E, n k), a_angle (T), each possibly null, and
+//   sbf_t  = sbe[kj] * Y,   sdot_t = a_sbe[kj] * Y + sbe[kj] * Y' a_angle[t],
+//   u_t    = sum_o w[., o] gS[o, t],   udot_t = sum_o a_w[., o] gS[o, t]
+// the second backward is
+//   gg_S[o, t]    = w[., o].sdot_t + a_w[., o].sbf_t                    (triplet_proj_bwd2_ggs)
+//   h_w[f, o]     = sum_t gS[o, t] sdot_t[f]                            (triplet_proj_bwd2_wgrad)
+//   h_sbe_rows[t] = udot_t * Y + u_t * Y' a_angle[t]                    (triplet_proj_bwd2_geom)
+//   h_angle[t]    = sum_f (udot_t sbe Y' + u_t a_sbe[kj] Y' + a_angle[t] u_t sbe Y'').
+
+// Y_l0 and its first two derivatives in theta from the Legendre recurrence in z = cos theta:
+// dY/dtheta = -sin P', d2Y/dtheta2 = sin^2 P'' - cos P' (regular at 0 and pi).  Y2 may be null.
+__device__ void legendre_y012(int n, float theta, const float* __restrict__ pref, float* Y,
+                              float* Y1, float* Y2, int stride) {
+  float st, ct;
+  sincosf(theta, &st, &ct);
+  float p2 = 0.f, d2 = 0.f, e2 = 0.f;  // P_{l-2}, P', P''
+  float p1 = 0.f, d1 = 0.f, e1 = 0.f;  // P_{l-1}
+  for (int l = 0; l < n; ++l) {
+    float p, d, e;
+    if (l == 0) {
+      p = 1.f, d = 0.f, e = 0.f;
+    } else if (l == 1) {
+      p = ct, d = 1.f, e = 0.f;
+    } else {
+      const float inv = 1.f / (float)l, c1 = (float)(2 * l - 1), c2 = (float)(l - 1);
+      p = (c1 * ct * p1 - c2 * p2) * inv;
+      d = (c1 * (p1 + ct * d1) - c2 * d2) * inv;
+      e = (c1 * (2.f * d1 + ct * e1) - c2 * e2) * inv;
+    }
+    p2 = p1, d2 = d1, e2 = e1, p1 = p, d1 = d, e1 = e;
+    const float f = pref[l * l];
+    Y[l * stride] = f * p;
+    Y1[l * stride] = -f * st * d;
+    if (Y2) Y2[l * stride] = f * (st * st * e - ct * d);
+  }
+}
+
+// stage_tile<false> with the gathered a_sbe rows (zeros if null), Y' and, where Y2L is given,
+// Y'' planes and the tile's a_angle (zeros if null).  Ends with a barrier.
+__device__ void stage_tile2(int64_t t0, int64_t T, int64_t E, int n, int nk,
+                            const float* __restrict__ jb, const float* __restrict__ a_jb,
+                            const float* __restrict__ angle, const float* __restrict__ a_angle,
+                            const int64_t* __restrict__ idx_kj, const float* __restrict__ pref,
+                            float* jbL, float* ajL, float* YL, float* Y1L, float* Y2L, float* aaL,
+                            int64_t* kjL) {
+  const int tid = threadIdx.x, nt = blockDim.x;
+  if (tid < kTile) {
+    const int64_t kj = t0 + tid < T ? idx_kj[t0 + tid] : -1;
+    kjL[tid] = kj < E ? kj : -1;
+    aaL[tid] = (a_angle && t0 + tid < T) ? a_angle[t0 + tid] : 0.f;
+  }
+  __syncthreads();
+  for (int i = tid; i < kTile * nk; i += nt) {
+    const int r = i / nk, c = i - r * nk;
+    const int64_t kj = kjL[r];
+    jbL[c * kLd + r] = kj >= 0 ? jb[kj * nk + c] : 0.f;
+    ajL[c * kLd + r] = (kj >= 0 && a_jb) ? a_jb[kj * nk + c] : 0.f;
+  }
+  if (tid < kTile) {
+    if (t0 + tid < T) {
+      legendre_y012(n, angle[t0 + tid], pref, YL + tid, Y1L + tid, Y2L ? Y2L + tid : nullptr,
+                    kLd);
+    } else {
+      for (int i = 0; i < n; ++i) {
+        YL[i * kLd + tid] = 0.f;
+        Y1L[i * kLd + tid] = 0.f;
+        if (Y2L) Y2L[i * kLd + tid] = 0.f;
+      }
+    }
+  }
+  __syncthreads();
+}
+
+// forward-shaped: one wave per tile, lane = triplet
+__global__ __launch_bounds__(kTile) void triplet_proj_bwd2_ggs(
+    int64_t T, int64_t E, int n, int k, const float* __restrict__ jb,
+    const float* __restrict__ a_jb, const float* __restrict__ angle,
+    const float* __restrict__ a_angle, const int64_t* __restrict__ idx_kj,
+    const float* __restrict__ pref, const float* __restrict__ w1t,
+    const float* __restrict__ a_w1t, int Oa, int oa_ld, int ba, float* __restrict__ ggS) {
+  extern __shared__ float sm[];
+  __shared__ int64_t kjL[kTile];
+  __shared__ float aaL[kTile];
+  const int nk = n * k;
+  float* jbL = sm;
+  float* ajL = jbL + nk * kLd;
+  float* YL = ajL + nk * kLd;
+  float* Y1L = YL + n * kLd;
+  const int lane = threadIdx.x;
+  for (int64_t t0 = (int64_t)blockIdx.x * kTile; t0 < T; t0 += (int64_t)gridDim.x * kTile) {
+    __syncthreads();
+    stage_tile2(t0, T, E, n, nk, jb, a_jb, angle, a_angle, idx_kj, pref, jbL, ajL, YL, Y1L,
+                nullptr, aaL, kjL);
+    const int64_t t = t0 + lane;
+    const float aa = aaL[lane];
+    for (int o0 = 0; o0 < Oa; o0 += kOC) {
+      float acc[kOC];
+#pragma unroll
+      for (int u = 0; u < kOC; ++u) acc[u] = 0.f;
+      for (int l = 0; l < n; ++l) {
+        const float y = YL[l * kLd + lane], y1a = Y1L[l * kLd + lane] * aa;
+        for (int q = 0; q < k; ++q) {
+          const int f = l * k + q;
+          const float s = jbL[f * kLd + lane];
+          const float sd = fmaf(ajL[f * kLd + lane], y, s * y1a);
+          const float* w = w1t + (int64_t)f * oa_ld + o0;
+#pragma unroll
+          for (int u = 0; u < kOC; ++u) acc[u] = fmaf(w[u], sd, acc[u]);
+          if (a_w1t) {
+            const float e = s * y;
+            const float* aw = a_w1t + (int64_t)f * oa_ld + o0;
+#pragma unroll
+            for (int u = 0; u < kOC; ++u) acc[u] = fmaf(aw[u], e, acc[u]);
+          }
+        }
+      }
+      if (t < T) {
+#pragma unroll
+        for (int u = 0; u < kOC; ++u) {
+          const int o = o0 + u;
+          if (o < Oa) ggS[proj_index(o, t, T, ba)] = acc[u];
+        }
+      }
+    }
+  }
+}
+
+// as triplet_proj_wgrad<false> with sdot in place of sbf: thread = feature, blockIdx.y = chunk of
+// kOC output columns, triplets added in index order, one partial row per block
+__global__ void triplet_proj_bwd2_wgrad(
+    int64_t T, int64_t E, int n, int k, int64_t tiles_per_block, const float* __restrict__ jb,
+    const float* __restrict__ a_jb, const float* __restrict__ angle,
+    const float* __restrict__ a_angle, const int64_t* __restrict__ idx_kj,
+    const float* __restrict__ pref, const float* __restrict__ gS, int Oa, int oa_ld, int ba,
+    float* __restrict__ partials) {
+  extern __shared__ float sm[];
+  __shared__ int64_t kjL[kTile];
+  __shared__ float aaL[kTile];
+  __shared__ float gL[kTile][kOC];
+  const int nk = n * k;
+  float* jbL = sm;
+  float* ajL = jbL + nk * kLd;
+  float* YL = ajL + nk * kLd;
+  float* Y1L = YL + n * kLd;
+  const int tid = threadIdx.x;
+  const int o0 = blockIdx.y * kOC;
+  const int f = tid;
+  const bool active = f < nk;
+  const int yrow = active ? f / k : 0;
+  float acc[kOC];
+#pragma unroll
+  for (int u = 0; u < kOC; ++u) acc[u] = 0.f;
+  const int64_t tile0 = (int64_t)blockIdx.x * tiles_per_block;
+  for (int64_t tile = tile0; tile < tile0 + tiles_per_block; ++tile) {
+    const int64_t t0 = tile * kTile;
+    if (t0 >= T) break;
+    __syncthreads();
+    stage_tile2(t0, T, E, n, nk, jb, a_jb, angle, a_angle, idx_kj, pref, jbL, ajL, YL, Y1L,
+                nullptr, aaL, kjL);
+    for (int i = tid; i < kTile * kOC; i += blockDim.x) {
+      const int r = i / kOC, u = i % kOC;
+      const int o = o0 + u;
+      const int64_t t = t0 + r;
+      gL[r][u] = (t < T && o < Oa) ? gS[proj_index(o, t, T, ba)] : 0.f;
+    }
+    __syncthreads();
+    if (active) {
+      for (int r = 0; r < kTile; ++r) {
+        const float sd = fmaf(ajL[f * kLd + r], YL[yrow * kLd + r],
+                              jbL[f * kLd + r] * Y1L[yrow * kLd + r] * aaL[r]);
+#pragma unroll
+        for (int u = 0; u < kOC; ++u) acc[u] = fmaf(gL[r][u], sd, acc[u]);
+      }
+    }
+  }
+  if (active) {
+    float* row = partials + (int64_t)blockIdx.x * nk * oa_ld;
+#pragma unroll
+    for (int u = 0; u < kOC; ++u) row[(int64_t)f * oa_ld + o0 + u] = acc[u];
+  }
+}
+
+// as triplet_proj_geom_bwd<false>: lane = triplet; u and udot are folded chunk by chunk into the
+// h_sbe row (LDS, written out coalesced) and h_angle (a register)
+__global__ __launch_bounds__(kTile) void triplet_proj_bwd2_geom(
+    int64_t T, int64_t E, int n, int k, const float* __restrict__ jb,
+    const float* __restrict__ a_jb, const float* __restrict__ angle,
+    const float* __restrict__ a_angle, const int64_t* __restrict__ idx_kj,
+    const float* __restrict__ pref, const float* __restrict__ w1t,
+    const float* __restrict__ a_w1t, int Oa, int oa_ld, int ba, const float* __restrict__ gS,
+    float* __restrict__ h_jb_rows, float* __restrict__ h_angle) {
+  extern __shared__ float sm[];
+  __shared__ int64_t kjL[kTile];
+  __shared__ float aaL[kTile];
+  const int nk = n * k;
+  float* jbL = sm;
+  float* ajL = jbL + nk * kLd;
+  float* hjL = ajL + nk * kLd;
+  float* YL = hjL + nk * kLd;
+  float* Y1L = YL + n * kLd;
+  float* Y2L = Y1L + n * kLd;
+  const int lane = threadIdx.x;
+  for (int64_t t0 = (int64_t)blockIdx.x * kTile; t0 < T; t0 += (int64_t)gridDim.x * kTile) {
+    __syncthreads();
+    stage_tile2(t0, T, E, n, nk, jb, a_jb, angle, a_angle, idx_kj, pref, jbL, ajL, YL, Y1L, Y2L,
+                aaL, kjL);
+    const int64_t t = t0 + lane;
+    const float aa = aaL[lane];
+    for (int i = 0; i < nk; ++i) hjL[i * kLd + lane] = 0.f;
+    float ha = 0.f;
+    for (int o0 = 0; o0 < Oa; o0 += kOC) {
+      float g[kOC];
+#pragma unroll
+      for (int u = 0; u < kOC; ++u) {
+        const int o = o0 + u;
+        g[u] = (t < T && o < Oa) ? gS[proj_index(o, t, T, ba)] : 0.f;
+      }
+      for (int l = 0; l < n; ++l) {
+        const float y = YL[l * kLd + lane], y1 = Y1L[l * kLd + lane];
+        const float y2a = Y2L[l * kLd + lane] * aa;
+        for (int q = 0; q < k; ++q) {
+          const int f = l * k + q;
+          const float* w = w1t + (int64_t)f * oa_ld + o0;
+          float ue = 0.f, ud = 0.f;
+#pragma unroll
+          for (int u = 0; u < kOC; ++u) ue = fmaf(w[u], g[u], ue);
+          if (a_w1t) {
+            const float* aw = a_w1t + (int64_t)f * oa_ld + o0;
+#pragma unroll
+            for (int u = 0; u < kOC; ++u) ud = fmaf(aw[u], g[u], ud);
+          }
+          const float s = jbL[f * kLd + lane], as = ajL[f * kLd + lane];
+          hjL[f * kLd + lane] += ud * y + ue * y1 * aa;
+          ha += ud * s * y1 + ue * (as * y1 + s * y2a);
+        }
+      }
+    }
+    if (t < T) h_angle[t] = ha;
+    __syncthreads();
+    for (int r = 0; r < kTile && t0 + r < T; ++r)
+      for (int c = lane; c < nk; c += kTile) h_jb_rows[(t0 + r) * nk + c] = hjL[c * kLd + r];
+  }
+}
+
 template <bool kTorsion>
 int64_t proj_bwd_blocks(int64_t T) {
   const int cap = kTorsion ? kProjBwdBlocks : kProjBwdBlocksAngleOnly;
@@ -597,6 +931,29 @@ int edge_basis_bwd_launch(const float* dist, int64_t n_edges, float cutoff, int 
   int rc = launch_status();
   if (rc != GMP_OK) return rc;
   return gmp_sum_rows_f32(freq_partials, nb, num_radial, grad_freq, stream);
+}
+
+template <bool kCut>
+int edge_basis_bwd2_launch(const float* dist, int64_t n_edges, float cutoff, int envelope_exponent,
+                           const float* freq, int num_radial, const float* zeros,
+                           const float* norm, int num_spherical, const float* grad_rbf,
+                           const float* grad_jb, const float* a_dist, const float* a_freq,
+                           float* gg_rbf, float* gg_jb, float* h_dist, float* h_freq,
+                           float* freq_partials, void* stream) {
+  GMP_CHECK_ARG(n_edges >= 0 && basis_ok(num_spherical, num_radial) && cutoff > 0.f &&
+                envelope_exponent >= 0 && h_freq);
+  if (n_edges == 0)
+    return hip_check(hipMemsetAsync(h_freq, 0, num_radial * sizeof(float), as_stream(stream)));
+  GMP_CHECK_ARG(dist && freq && zeros && norm && gg_rbf && gg_jb && h_dist && freq_partials);
+  const int64_t nb = ceil_div(n_edges, kEdgeT);
+  GMP_CHECK_ARG(nb <= INT32_MAX);
+  edge_basis_bwd2<kCut><<<(unsigned)nb, kEdgeT, 0, as_stream(stream)>>>(
+      dist, n_edges, cutoff, envelope_exponent, freq, num_radial, zeros, norm,
+      num_spherical * num_radial, grad_rbf, grad_jb, a_dist, a_freq, gg_rbf, gg_jb, h_dist,
+      freq_partials);
+  int rc = launch_status();
+  if (rc != GMP_OK) return rc;
+  return gmp_sum_rows_f32(freq_partials, nb, num_radial, h_freq, stream);
 }
 
 // The per-triplet launchers take SphereNet's argument lists; without kTorsion the torsion
@@ -677,6 +1034,49 @@ int triplet_proj_bwd_launch(int64_t n_triplets, int64_t n_edges, int n, int k, c
   return rc;
 }
 
+int triplet_proj_bwd2_launch(int64_t n_triplets, int64_t n_edges, int n, int k, const float* jb,
+                             const float* angle, const int64_t* idx_kj, const float* pref,
+                             const float* w_sbf1_t, int n_layers, int ba, const float* grad_S,
+                             const float* a_jb, const float* a_angle, const float* a_w_t,
+                             float* gg_S, float* h_w, float* partials, float* h_jb_rows,
+                             float* h_angle, void* stream) {
+  GMP_CHECK_ARG(n_triplets >= 0 && n_edges >= 0 && basis_ok(n, k) && n_layers >= 1 && ba >= 1 &&
+                h_w);
+  const int nk = n * k;
+  const int Oa = n_layers * ba;
+  const int oa_ld = (int)ceil_div(Oa, kOC) * kOC;
+  const int64_t width = (int64_t)nk * oa_ld;
+  hipStream_t s = as_stream(stream);
+  if (n_triplets == 0) return hip_check(hipMemsetAsync(h_w, 0, width * sizeof(float), s));
+  GMP_CHECK_ARG(jb && angle && idx_kj && pref && w_sbf1_t && grad_S && gg_S && partials &&
+                n_edges > 0 && (!h_jb_rows == !h_angle));
+  const int threads = (int)ceil_div(nk, kWave) * kWave;
+  const size_t lds2 = (size_t)(2 * nk + 2 * n) * kLd * sizeof(float);
+  const size_t lds3 = (size_t)(3 * nk + 3 * n) * kLd * sizeof(float);
+  if (threads > 1024 || lds2 > kLdsCap || (h_angle && lds3 > kLdsCap)) return GMP_ERR_UNSUPPORTED;
+  triplet_proj_bwd2_ggs<<<tile_grid(n_triplets), kTile, lds2, s>>>(
+      n_triplets, n_edges, n, k, jb, a_jb, angle, a_angle, idx_kj, pref, w_sbf1_t, a_w_t, Oa,
+      oa_ld, ba, gg_S);
+  int rc = launch_status();
+  if (rc != GMP_OK) return rc;
+  const int64_t nb = proj_bwd_blocks<false>(n_triplets);
+  const int64_t tpb = ceil_div(ceil_div(n_triplets, kTile), nb);
+  triplet_proj_bwd2_wgrad<<<dim3((unsigned)nb, (unsigned)(oa_ld / kOC)), threads, lds2, s>>>(
+      n_triplets, n_edges, n, k, tpb, jb, a_jb, angle, a_angle, idx_kj, pref, grad_S, Oa, oa_ld,
+      ba, partials);
+  rc = launch_status();
+  if (rc != GMP_OK) return rc;
+  rc = gmp_sum_rows_f32(partials, nb, width, h_w, stream);
+  if (rc != GMP_OK) return rc;
+  if (h_angle) {
+    triplet_proj_bwd2_geom<<<tile_grid(n_triplets), kTile, lds3, s>>>(
+        n_triplets, n_edges, n, k, jb, a_jb, angle, a_angle, idx_kj, pref, w_sbf1_t, a_w_t, Oa,
+        oa_ld, ba, grad_S, h_jb_rows, h_angle);
+    rc = launch_status();
+  }
+  return rc;
+}
+
 }  // namespace
 }  // namespace gmp
 
@@ -726,6 +1126,23 @@ int gmp_dime_edge_basis_bwd_f32(const float* dist, int64_t n_edges, float cutoff
   return edge_basis_bwd_launch<true>(dist, n_edges, cutoff, envelope_exponent, freq, num_radial,
                                      zeros, norm, num_spherical, grad_rbf, grad_sbe, grad_dist,
                                      grad_freq, freq_partials, stream);
+}
+
+int64_t gmp_dime_edge_basis_bwd2_partial_rows(int64_t n_edges) {
+  return edge_basis_bwd_partial_rows(n_edges);
+}
+
+int gmp_dime_edge_basis_bwd2_f32(const float* dist, int64_t n_edges, float cutoff,
+                                 int envelope_exponent, const float* freq, int num_radial,
+                                 const float* zeros, const float* norm, int num_spherical,
+                                 const float* grad_rbf, const float* grad_sbe,
+                                 const float* a_dist, const float* a_freq, float* gg_rbf,
+                                 float* gg_sbe, float* h_dist, float* h_freq,
+                                 float* freq_partials, void* stream) {
+  return edge_basis_bwd2_launch<true>(dist, n_edges, cutoff, envelope_exponent, freq, num_radial,
+                                      zeros, norm, num_spherical, grad_rbf, grad_sbe, a_dist,
+                                      a_freq, gg_rbf, gg_sbe, h_dist, h_freq, freq_partials,
+                                      stream);
 }
 
 int gmp_sph_triplet_proj_fwd_f32(int64_t n_triplets, int64_t n_edges, int num_spherical,
@@ -793,6 +1210,22 @@ int gmp_dime_triplet_proj_bwd_f32(int64_t n_triplets, int64_t n_edges, int num_s
                                         nullptr, idx_kj, pref, w_sbf1_t, n_layers, b, nullptr, 0,
                                         grad_S, nullptr, grad_w, partials, grad_sbe_rows,
                                         grad_angle, nullptr, stream);
+}
+
+int64_t gmp_dime_triplet_proj_bwd2_partial_rows(int64_t n_triplets) {
+  return proj_bwd_blocks<false>(n_triplets);
+}
+
+int gmp_dime_triplet_proj_bwd2_f32(int64_t n_triplets, int64_t n_edges, int num_spherical,
+                                   int num_radial, const float* sbe, const float* angle,
+                                   const int64_t* idx_kj, const float* pref,
+                                   const float* w_sbf1_t, int n_layers, int b,
+                                   const float* grad_S, const float* a_sbe, const float* a_angle,
+                                   const float* a_w_t, float* gg_S, float* h_w, float* partials,
+                                   float* h_sbe_rows, float* h_angle, void* stream) {
+  return triplet_proj_bwd2_launch(n_triplets, n_edges, num_spherical, num_radial, sbe, angle,
+                                  idx_kj, pref, w_sbf1_t, n_layers, b, grad_S, a_sbe, a_angle,
+                                  a_w_t, gg_S, h_w, partials, h_sbe_rows, h_angle, stream);
 }
 
 }  // extern "C"

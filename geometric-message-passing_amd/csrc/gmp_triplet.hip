@@ -252,6 +252,106 @@ __global__ void triplet_geom_bwd_kernel(const float* __restrict__ pos,
   }
 }
 
+// Second backward of dist and angle (energy-and-force training, dimenet.py:82-89 differentiated
+// twice): the first backward's rows are linear in (g_dist, g_angle) and non-linear in pos; with
+// the cotangent a (N, 3) of d pos this kernel returns
+//   gg_dist[e]  = (a_i - a_j).(p_i - p_j) / d,   gg_angle[t] = a_u.dtheta/du + a_v.dtheta/dv
+//   (a_u = a[ue] - a[vtx], a_v = a[k] - a[vtx]), and
+//   rows: the directional derivative along (a_u, a_v) / (a_i - a_j) of the rows that
+//   triplet_geom_bwd_kernel writes (= g Hess(theta) (a_u, a_v), g Hess(d) (a_i - a_j)), in the
+//   same layout with the same node[], so the same segmented sum yields h_pos.
+// Forward mode (value + tangent) of the formulas above; the differences are taken in fp32 as
+// there, the rest runs in double and is rounded once (second derivatives divide by b^2, d^2).
+// Dead cases as the first backward: b = 0 drops the c^ terms and their tangents, len = 0 and
+// g == 0 write zero rows (gg_* is still written).
+struct D3 {
+  double x, y, z;
+};
+__device__ __forceinline__ D3 dd3(V3 a) { return D3{(double)a.x, (double)a.y, (double)a.z}; }
+__device__ __forceinline__ D3 dxf(D3 a, D3 b) {
+  return D3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
+}
+__device__ __forceinline__ double ddot(D3 a, D3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+__device__ __forceinline__ D3 dadd(D3 a, D3 b) { return D3{a.x + b.x, a.y + b.y, a.z + b.z}; }
+__device__ __forceinline__ D3 dscale(double s, D3 a) { return D3{s * a.x, s * a.y, s * a.z}; }
+__device__ __forceinline__ void st3(float* r, D3 a) {
+  r[0] = (float)a.x; r[1] = (float)a.y; r[2] = (float)a.z;
+}
+
+__global__ void triplet_geom_bwd2_kernel(const float* __restrict__ pos,
+                                         const int64_t* __restrict__ ei, int64_t E,
+                                         const int64_t* __restrict__ idx_kj,
+                                         const int64_t* __restrict__ idx_ji, int64_t T, int mode,
+                                         const float* __restrict__ g_dist,
+                                         const float* __restrict__ g_angle,
+                                         const float* __restrict__ a_pos,
+                                         float* __restrict__ gg_dist,
+                                         float* __restrict__ gg_angle, float* __restrict__ rows,
+                                         int64_t* __restrict__ node) {
+  const int64_t n = T + E;
+  for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < n;
+       q += (int64_t)gridDim.x * blockDim.x) {
+    if (q < T) {
+      const int64_t t = q, e = idx_ji[t];
+      const int64_t j = ei[e], i = ei[E + e], k = ei[idx_kj[t]];
+      const int64_t vtx = mode == 0 ? j : i, ue = mode == 0 ? i : j;
+      const V3 pv = ld3(pos, vtx), av = ld3(a_pos, vtx);
+      const D3 u = dd3(sub3(ld3(pos, ue), pv)), v = dd3(sub3(ld3(pos, k), pv));
+      const D3 du = dd3(sub3(ld3(a_pos, ue), av)), dv = dd3(sub3(ld3(a_pos, k), av));
+      const double g = g_angle ? (double)g_angle[t] : 0.0;
+      const D3 c = dxf(u, v), dc = dadd(dxf(du, v), dxf(u, dv));
+      const double b = sqrt(ddot(c, c)), a = ddot(u, v);
+      const double da = ddot(du, v) + ddot(u, dv);
+      const double db = b > 0.0 ? ddot(c, dc) / b : 0.0;
+      const double den = a * a + b * b;
+      D3 hu{0.0, 0.0, 0.0}, hv{0.0, 0.0, 0.0};
+      double gg = 0.0;
+      if (den > 0.0) {
+        gg = (a * db - b * da) / den;
+        if (g != 0.0) {
+          const double dden = 2.0 * (a * da + b * db);
+          const double ga = -g * b / den, gb = g * a / den;
+          const double dga = -g * (db / den - b * dden / (den * den));
+          const double dgb = g * (da / den - a * dden / (den * den));
+          hu = dadd(dscale(dga, v), dscale(ga, dv));
+          hv = dadd(dscale(dga, u), dscale(ga, du));
+          if (b > 0.0) {
+            const D3 ch = dscale(1.0 / b, c);
+            const D3 dch = dadd(dscale(1.0 / b, dc), dscale(-db / (b * b), c));
+            hu = dadd(hu, dadd(dscale(dgb, dxf(v, ch)),
+                               dscale(gb, dadd(dxf(dv, ch), dxf(v, dch)))));
+            hv = dadd(hv, dadd(dscale(dgb, dxf(ch, u)),
+                               dscale(gb, dadd(dxf(dch, u), dxf(ch, du)))));
+          }
+        }
+      }
+      if (gg_angle) gg_angle[t] = (float)gg;
+      st3(rows + 3 * t, dscale(-1.0, dadd(hu, hv)));
+      st3(rows + 3 * (T + t), hu);
+      st3(rows + 3 * (2 * T + t), hv);
+      node[t] = vtx;
+      node[T + t] = ue;
+      node[2 * T + t] = k;
+    } else {
+      const int64_t e = q - T;
+      const int64_t j = ei[e], i = ei[E + e];
+      const D3 d = dd3(sub3(ld3(pos, i), ld3(pos, j)));
+      const D3 dd = dd3(sub3(ld3(a_pos, i), ld3(a_pos, j)));
+      const double len = sqrt(ddot(d, d));
+      const double g = g_dist ? (double)g_dist[e] : 0.0;
+      const double dlen = len > 0.0 ? ddot(d, dd) / len : 0.0;
+      D3 h{0.0, 0.0, 0.0};
+      if (g != 0.0 && len > 0.0)
+        h = dadd(dscale(g / len, dd), dscale(-g * dlen / (len * len), d));
+      if (gg_dist) gg_dist[e] = (float)dlen;
+      st3(rows + 3 * (3 * T + e), h);
+      st3(rows + 3 * (3 * T + E + e), dscale(-1.0, h));
+      node[3 * T + e] = i;
+      node[3 * T + E + e] = j;
+    }
+  }
+}
+
 // Backward of the SphereNet torsion w.r.t. pos (spherenet_layer.py:535-559 under autograd): the
 // scatter-min routes the gradient to the winning candidate k_n (torch_scatter's arg), whose
 // torsion1 = atan2(b, a) with u = p_i - p_j, v = p_k - p_j, w = p_kn - p_j,
@@ -357,6 +457,21 @@ int gmp_triplet_geom_bwd_f32(const float* pos, const int64_t* edge_index, int64_
   triplet_geom_bwd_kernel<<<grid_for(n_edges + n_triplets), 256, 0, as_stream(stream)>>>(
       pos, edge_index, n_edges, idx_kj, idx_ji, n_triplets, mode, grad_dist, grad_angle, rows,
       node);
+  return launch_status();
+}
+
+int gmp_triplet_geom_bwd2_f32(const float* pos, const int64_t* edge_index, int64_t n_edges,
+                              const int64_t* idx_kj, const int64_t* idx_ji, int64_t n_triplets,
+                              int mode, const float* grad_dist, const float* grad_angle,
+                              const float* a_pos, float* gg_dist, float* gg_angle, float* rows,
+                              int64_t* node, void* stream) {
+  GMP_CHECK_ARG(n_edges >= 0 && n_triplets >= 0 && (mode == 0 || mode == 1));
+  if (n_edges + n_triplets == 0) return GMP_OK;
+  GMP_CHECK_ARG(pos && a_pos && edge_index && rows && node &&
+                (n_triplets == 0 || (idx_kj && idx_ji)));
+  triplet_geom_bwd2_kernel<<<grid_for(n_edges + n_triplets), 256, 0, as_stream(stream)>>>(
+      pos, edge_index, n_edges, idx_kj, idx_ji, n_triplets, mode, grad_dist, grad_angle, a_pos,
+      gg_dist, gg_angle, rows, node);
   return launch_status();
 }
 

@@ -2015,6 +2015,64 @@ std::tuple<Tensor, Tensor, Tensor> dime_triplet_proj_bwd(
   return {gw, gsb, ga};
 }
 
+// second backward of the edge basis: (gg_rbf, gg_sbe, h_dist, h_freq)
+std::tuple<Tensor, Tensor, Tensor, Tensor> dime_edge_basis_bwd2(
+    const Tensor& dist, const Tensor& freq, const Tensor& zeros, const Tensor& norm, double cutoff,
+    int64_t envelope_exponent, const optional<Tensor>& grad_rbf, const optional<Tensor>& grad_sbe,
+    const optional<Tensor>& a_dist, const optional<Tensor>& a_freq) {
+  OpGuard g(dist, "dime_edge_basis_bwd2");
+  f32(dist, "dist");
+  f32(freq, "freq");
+  int64_t n, k;
+  sph_tables(zeros, norm, &n, &k);
+  TORCH_CHECK(dist.dim() == 1, "gmp.dime_edge_basis_bwd2: dist (E)");
+  numel(freq, k, "freq");
+  const int64_t E = dist.numel();
+  opt_f32(grad_rbf, {E, k}, "grad_rbf");
+  opt_f32(grad_sbe, {E, n * k}, "grad_sbe");
+  opt_f32(a_dist, {E}, "a_dist");
+  opt_f32(a_freq, {k}, "a_freq");
+  auto o = dist.options();
+  Tensor ggr = at::empty({E, k}, o), ggs = at::empty({E, n * k}, o);
+  Tensor hd = at::empty({E}, o), hf = at::empty({k}, o);
+  Tensor part = at::empty({gmp_dime_edge_basis_bwd2_partial_rows(E), k}, o);
+  check_rc(gmp_dime_edge_basis_bwd2_f32(fp(dist), E, (float)cutoff, (int)envelope_exponent,
+                                        fp(freq), (int)k, fp(zeros), fp(norm), (int)n,
+                                        cfp(grad_rbf), cfp(grad_sbe), cfp(a_dist), cfp(a_freq),
+                                        fp(ggr), fp(ggs), fp(hd), fp(hf), fp(part), cur_stream()),
+           "gmp_dime_edge_basis_bwd2_f32");
+  return {ggr, ggs, hd, hf};
+}
+
+// second backward of the projection: (gg_S (L, T, b), h_w_sbf1_t, h_sbe_rows (T, n k),
+// h_angle (T)); the last two are empty without want_geometry
+std::tuple<Tensor, Tensor, Tensor, Tensor> dime_triplet_proj_bwd2(
+    const Tensor& sbe, const Tensor& angle, const Tensor& idx_kj, const Tensor& pref,
+    const Tensor& wt, int64_t n, int64_t k, int64_t L, int64_t b, const Tensor& gS,
+    const optional<Tensor>& a_sbe, const optional<Tensor>& a_angle, const optional<Tensor>& a_wt,
+    bool want_geometry) {
+  OpGuard g(sbe, "dime_triplet_proj_bwd2");
+  const int64_t T = dime_triplet_args(sbe, angle, idx_kj, pref, n, k);
+  dime_proj_weights(wt, n, k, L, b);
+  f32(gS, "grad_S");
+  shape(gS, {L, T, b}, "grad_S");
+  opt_f32(a_sbe, sbe.sizes(), "a_sbe");
+  opt_f32(a_angle, {T}, "a_angle");
+  opt_f32(a_wt, wt.sizes(), "a_w_sbf1_t");
+  auto o = sbe.options();
+  Tensor ggS = at::empty({L, T, b}, o), hw = at::empty_like(wt);
+  Tensor part = at::empty({gmp_dime_triplet_proj_bwd2_partial_rows(T), wt.numel()}, o);
+  const int64_t Tg = want_geometry ? T : 0;
+  Tensor hsb = at::empty({Tg, n * k}, o), ha = at::empty({Tg}, o);
+  check_rc(gmp_dime_triplet_proj_bwd2_f32(T, sbe.size(0), (int)n, (int)k, fp(sbe), fp(angle),
+                                          ip(idx_kj), fp(pref), fp(wt), (int)L, (int)b, fp(gS),
+                                          cfp(a_sbe), cfp(a_angle), cfp(a_wt), fp(ggS), fp(hw),
+                                          fp(part), want_geometry ? fp(hsb) : nullptr,
+                                          want_geometry ? fp(ha) : nullptr, cur_stream()),
+           "gmp_dime_triplet_proj_bwd2_f32");
+  return {ggS, hw, hsb, ha};
+}
+
 void interact1_args(const Tensor& S, const Tensor& w) {
   f32(S, "S");
   f32(w, "w_sbf2");
@@ -2411,6 +2469,24 @@ std::tuple<Tensor, Tensor, Tensor> dime_triplet_proj_bwd(
   auto o = sbe.options();
   return {at::empty_like(wt), at::empty({Tg, n * k}, o), at::empty({Tg}, o)};
 }
+std::tuple<Tensor, Tensor, Tensor, Tensor> dime_edge_basis_bwd2(
+    const Tensor& dist, const Tensor& freq, const Tensor& zeros, const Tensor&, double, int64_t,
+    const optional<Tensor>&, const optional<Tensor>&, const optional<Tensor>&,
+    const optional<Tensor>&) {
+  const int64_t E = dist.numel(), k = freq.numel();
+  auto o = dist.options();
+  return {at::empty({E, k}, o), at::empty({E, zeros.numel()}, o), at::empty({E}, o),
+          at::empty({k}, o)};
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor> dime_triplet_proj_bwd2(
+    const Tensor& sbe, const Tensor& angle, const Tensor&, const Tensor&, const Tensor& wt,
+    int64_t n, int64_t k, int64_t L, int64_t b, const Tensor&, const optional<Tensor>&,
+    const optional<Tensor>&, const optional<Tensor>&, bool want_geometry) {
+  const int64_t T = angle.numel(), Tg = want_geometry ? T : 0;
+  auto o = sbe.options();
+  return {at::empty({L, T, b}, o), at::empty_like(wt), at::empty({Tg, n * k}, o),
+          at::empty({Tg}, o)};
+}
 Tensor triplet_interact1_fwd(const Tensor& src, const Tensor&, const Tensor& w, const Tensor&,
                              const optional<Tensor>&, const Tensor& rowptr) {
   return at::empty({rowptr.numel() - 1, w.size(0)}, src.options());
@@ -2575,6 +2651,13 @@ TORCH_LIBRARY(gmp, m) {
   m.def("dime_triplet_proj_bwd(Tensor sbe, Tensor angle, Tensor idx_kj, Tensor pref, "
         "Tensor w_sbf1_t, int num_spherical, int num_radial, int n_layers, int b, Tensor grad_S, "
         "bool want_geometry) -> (Tensor grad_w_sbf1_t, Tensor grad_sbe_rows, Tensor grad_angle)");
+  m.def("dime_edge_basis_bwd2(Tensor dist, Tensor freq, Tensor zeros, Tensor norm, float cutoff, "
+        "int envelope_exponent, Tensor? grad_rbf, Tensor? grad_sbe, Tensor? a_dist, "
+        "Tensor? a_freq) -> (Tensor gg_rbf, Tensor gg_sbe, Tensor h_dist, Tensor h_freq)");
+  m.def("dime_triplet_proj_bwd2(Tensor sbe, Tensor angle, Tensor idx_kj, Tensor pref, "
+        "Tensor w_sbf1_t, int num_spherical, int num_radial, int n_layers, int b, Tensor grad_S, "
+        "Tensor? a_sbe, Tensor? a_angle, Tensor? a_w_sbf1_t, bool want_geometry) -> "
+        "(Tensor gg_S, Tensor h_w_sbf1_t, Tensor h_sbe_rows, Tensor h_angle)");
   m.def("triplet_interact1_fwd(Tensor src, Tensor S, Tensor w_sbf2, Tensor gather_idx, "
         "Tensor? perm, Tensor rowptr) -> Tensor");
   m.def("triplet_interact1_bwd(Tensor grad_m, Tensor xd, Tensor S, Tensor w_sbf2, Tensor idx_kj, "
@@ -2655,6 +2738,8 @@ TORCH_LIBRARY(gmp, m) {
   m.impl("dime_triplet_proj_fwd", ns dime_triplet_proj_fwd);              \
   m.impl("dime_triplet_emb", ns dime_triplet_emb);                        \
   m.impl("dime_triplet_proj_bwd", ns dime_triplet_proj_bwd);              \
+  m.impl("dime_edge_basis_bwd2", ns dime_edge_basis_bwd2);                \
+  m.impl("dime_triplet_proj_bwd2", ns dime_triplet_proj_bwd2);            \
   m.impl("triplet_interact1_fwd", ns triplet_interact1_fwd);              \
   m.impl("triplet_interact1_bwd", ns triplet_interact1_bwd);
 

@@ -271,6 +271,15 @@ SIGNATURES = {
     "gmp_dime_triplet_proj_bwd_partial_rows": (c_i64, [c_i64]),
     "gmp_dime_triplet_proj_bwd_f32": (c_int, [c_i64, c_i64, c_int, c_int] + [c_vp] * 5
                                       + [c_int, c_int] + [c_vp] * 6),
+    # second backwards (DimeNet++ energy-and-force training); additions only
+    "gmp_triplet_geom_bwd2_f32": (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_int]
+                                  + [c_vp] * 8),
+    "gmp_dime_edge_basis_bwd2_partial_rows": (c_i64, [c_i64]),
+    "gmp_dime_edge_basis_bwd2_f32": (c_int, [c_vp, c_i64, c_f32, c_int, c_vp, c_int, c_vp, c_vp,
+                                             c_int] + [c_vp] * 10),
+    "gmp_dime_triplet_proj_bwd2_partial_rows": (c_i64, [c_i64]),
+    "gmp_dime_triplet_proj_bwd2_f32": (c_int, [c_i64, c_i64, c_int, c_int] + [c_vp] * 5
+                                       + [c_int, c_int] + [c_vp] * 10),
     "gmp_triplet_interact1_fwd_f32": (c_int, [c_i64, c_i64, c_i64, c_i64, c_int] + [c_vp] * 8),
     "gmp_triplet_interact1_bwd_partial_rows": (c_i64, [c_i64]),
     "gmp_triplet_interact1_bwd_f32": (c_int, [c_i64, c_i64, c_i64, c_int] + [c_vp] * 10),

@@ -32,6 +32,14 @@ def _activation(act):
     raise ValueError(f"DimeNetPPModel: unknown activation {act!r} (use 'swish' or a callable)")
 
 
+def _segment_sum(x, csr, twice):
+    """The segmented sum as today's SegmentReduceFn, or through ops.segment_reduce_fn (recorded
+    backward inside second_order()) on the twice-differentiable path."""
+    if twice:
+        return ops.segment_reduce_fn(x, csr, "sum")
+    return ops.SegmentReduceFn.apply(x, csr, "sum")
+
+
 class BesselBasisLayer(torch.nn.Module):
     """Holds freq; the values come from K18d together with sbe (DimeNetPPModel.bases)."""
 
@@ -112,14 +120,15 @@ class InteractionPPBlock(torch.nn.Module):
         for res_layer in list(self.layers_before_skip) + list(self.layers_after_skip):
             res_layer.reset_parameters()
 
-    def forward(self, x, rbf, S, idx_kj, idx_ji, offsets):
+    def forward(self, x, rbf, S, idx_kj, idx_ji, offsets, twice=False):
         """x (E, hidden): the edge features; S (T, basis_emb_size): this block's first
-        projection lin_sbf1(sbf) from K18d."""
+        projection lin_sbf1(sbf) from K18d.  twice: record the twice-differentiable K19d."""
         x_ji = self.act(ops.linear(x, self.lin_ji.weight, self.lin_ji.bias))
         x_kj = self.act(ops.linear(x, self.lin_kj.weight, self.lin_kj.bias))
         rbf = ops.linear(ops.linear(rbf, self.lin_rbf1.weight), self.lin_rbf2.weight)
         x_kj = self.act(ops.linear(x_kj * rbf, self.lin_down.weight))
-        m = ops.TripletInteract1Fn.apply(x_kj, S, self.lin_sbf2.weight, idx_kj, idx_ji, offsets)
+        interact = ops.TripletInteract1_2Fn if twice else ops.TripletInteract1Fn
+        m = interact.apply(x_kj, S, self.lin_sbf2.weight, idx_kj, idx_ji, offsets)
         h = x_ji + self.act(ops.linear(m, self.lin_up.weight))
         for layer in self.layers_before_skip:
             h = layer(h)
@@ -149,10 +158,10 @@ class OutputPPBlock(torch.nn.Module):
             lin.bias.data.fill_(0)
         self.lin.weight.data.fill_(0)
 
-    def forward(self, x, rbf, i, num_nodes):
+    def forward(self, x, rbf, i, num_nodes, twice=False):
         """Sum of lin_rbf(rbf) * x over each node's incoming edges, then the output MLP."""
         x = ops.linear(rbf, self.lin_rbf.weight) * x
-        v = ops.SegmentReduceFn.apply(x, ops.checked_csr(i, num_nodes), "sum")
+        v = _segment_sum(x, ops.checked_csr(i, num_nodes), twice)
         v = ops.linear(v, self.lin_up.weight)
         for lin in self.lins:
             v = self.act(ops.linear(v, lin.weight, lin.bias))
@@ -162,13 +171,19 @@ class OutputPPBlock(torch.nn.Module):
 class DimeNetPPModel(torch.nn.Module):
     """DimeNet++, "Fast and Uncertainty-Aware Directional Message Passing for Non-Equilibrium
     Molecules" (models/dimenet.py).  in_dim and max_num_neighbors are accepted and unused, as in
-    the reference (its forward takes batch.edge_index)."""
+    the reference (its forward takes batch.edge_index).
+
+    twice_differentiable (keyword-only; a plain attribute, not in the state_dict): inside
+    gmp_amd.second_order() the model records twice-differentiable Functions (K11, K18d and K19d
+    with their *_bwd2 kernels), so a loss on the forces -dE/dpos can be trained.  False, or
+    outside the context: the once-differentiable path, on which a second backward raises."""
 
     def __init__(self, hidden_channels=128, in_dim=1, out_dim=1, num_layers=4, int_emb_size=64,
                  basis_emb_size=8, out_emb_channels=256, num_spherical=7, num_radial=6, cutoff=10,
                  max_num_neighbors=32, envelope_exponent=5, num_before_skip=1, num_after_skip=2,
-                 num_output_layers=3, act='swish'):
+                 num_output_layers=3, act='swish', *, twice_differentiable=False):
         super().__init__()
+        self.twice_differentiable = bool(twice_differentiable)
         if num_spherical < 2:
             raise ValueError("num_spherical should be greater than 1")
         act = _activation(act)
@@ -194,10 +209,28 @@ class DimeNetPPModel(torch.nn.Module):
         for interaction in self.interaction_blocks:
             interaction.reset_parameters()
 
+    def _twice(self):
+        return bool(getattr(self, "twice_differentiable", False)) and ops.second_order_enabled()
+
     def bases(self, dist):
         """(rbf (E, k), sbe (E, n k)): the per-edge parts of the two bases from K18d."""
-        return ops.DimeEdgeBasisFn.apply(dist, self.rbf.freq, self.sbf.zeros, self.sbf.norm,
-                                         self.cutoff, self.envelope_exponent)
+        fn = ops.DimeEdgeBasis2Fn if self._twice() else ops.DimeEdgeBasisFn
+        return fn.apply(dist, self.rbf.freq, self.sbf.zeros, self.sbf.norm, self.cutoff,
+                        self.envelope_exponent)
+
+    def projections(self, sbe, angle, idx_kj):
+        """S[l] (T, basis_emb_size) = lin_sbf1 of block l applied to sbf, for every block (K18d)."""
+        blocks = self.interaction_blocks
+        L, n, k = len(blocks), self.num_spherical, self.num_radial
+        if not L:
+            return ()
+        weights = [blk.lin_sbf1.weight for blk in blocks]
+        if self._twice():
+            wt = ops.dime_feature_major(weights, n * k)
+            S = ops.DimeTripletProj2Fn.apply(sbe, angle, wt, idx_kj, self.sbf.pref, n, k, L,
+                                             weights[0].shape[0])
+            return S.unbind(0)
+        return ops.DimeTripletProjFn.apply(sbe, angle, idx_kj, self.sbf.pref, n, k, L, *weights)
 
     def forward(self, batch):
         if getattr(batch, "edge_shift_idx", None) is not None:
@@ -205,9 +238,11 @@ class DimeNetPPModel(torch.nn.Module):
                                       "supported: K11's triplets take no periodic images")
         z, pos, edge_index = batch.atoms, batch.pos, batch.edge_index
         ops._need_cuda(z, pos, edge_index, batch.batch)
-        if pos.requires_grad and torch.is_grad_enabled():
+        twice = self._twice()
+        if pos.requires_grad and torch.is_grad_enabled() and not twice:
             pos = ops.FirstOrderOnlyFn.apply(pos)  # forces yes, training through them no
-        dist, angle, i, j, _, _, _, idx_kj, idx_ji = dimenet_angles(pos, edge_index, z.size(0))
+        dist, angle, i, j, _, _, _, idx_kj, idx_ji = dimenet_angles(
+            pos, edge_index, z.size(0), twice_differentiable=twice)
         return self.forward_from_geometry(z, dist, angle, i, j, idx_kj, idx_ji, batch.batch,
                                           num_graphs=getattr(batch, "num_graphs", None))
 
@@ -216,21 +251,19 @@ class DimeNetPPModel(torch.nn.Module):
         """The model downstream of dimenet_angles: dist (E), angle (T, at vertex i), i / j (E)
         the target / source of each edge, idx_kj / idx_ji (T) the edges of each triplet with
         idx_ji non-decreasing (as K11 and PyG emit it), batch (N).  -> (num_graphs, out_dim).
-        Gradients flow to dist and angle (and through TripletGeomFn to pos)."""
+        Gradients flow to dist and angle (and through TripletGeomFn to pos); twice
+        differentiable where twice_differentiable is set inside gmp_amd.second_order()."""
         ops._need_cuda(atoms, dist, angle, i, j, idx_kj, idx_ji, batch)
         N, E, L = atoms.size(0), dist.numel(), len(self.interaction_blocks)
         if num_graphs is None:
             num_graphs = int(batch.max().item()) + 1 if N else 0
         offsets = triplet_offsets(idx_ji, E)
+        twice = self._twice()
         rbf, sbe = self.bases(dist)
-        S = ()
-        if L:
-            S = ops.DimeTripletProjFn.apply(
-                sbe, angle, idx_kj, self.sbf.pref, self.num_spherical, self.num_radial, L,
-                *[blk.lin_sbf1.weight for blk in self.interaction_blocks])
+        S = self.projections(sbe, angle, idx_kj)
         x = self.emb(atoms, rbf, i, j)
-        P = self.output_blocks[0](x, rbf, i, N)
+        P = self.output_blocks[0](x, rbf, i, N, twice)
         for l, blk in enumerate(self.interaction_blocks):
-            x = blk(x, rbf, S[l], idx_kj, idx_ji, offsets)
-            P = P + self.output_blocks[l + 1](x, rbf, i, N)
-        return ops.SegmentReduceFn.apply(P, ops.checked_csr(batch, num_graphs), "sum")
+            x = blk(x, rbf, S[l], idx_kj, idx_ji, offsets, twice)
+            P = P + self.output_blocks[l + 1](x, rbf, i, N, twice)
+        return _segment_sum(P, ops.checked_csr(batch, num_graphs), twice)

@@ -1,10 +1,11 @@
-"""Energy-and-force evaluation: F = -dE/dpos through the twice-differentiable SchNet path, and
-the stress of a periodic structure.
+"""Energy-and-force evaluation: F = -dE/dpos through the twice-differentiable SchNet and
+DimeNet++ paths, and the stress of a periodic structure.
 
 A loss on the forces needs the gradient of a gradient.  Inside `second_order()` (gmp_amd.ops) the
-SchNet path records autograd Functions whose backward is itself recorded, so the forces returned
-here (create_graph=True) can be trained on.  EGNN, GVP, TFN and MACE keep once-differentiable
-Functions: a second-order backward through them raises.
+SchNet path, and a DimeNetPPModel built (or set) with twice_differentiable=True, record autograd
+Functions whose backward is itself recorded, so the forces returned here (create_graph=True) can
+be trained on.  EGNN, GVP, TFN, MACE, SphereNet and a DimeNetPPModel without the flag keep
+once-differentiable Functions: a second-order backward through them raises.
 """
 import copy
 

@@ -1010,8 +1010,10 @@ def second_order_enabled():
 class second_order:
     """Context manager: record twice-differentiable Functions on the SchNet path (CFConv with a
     differentiable cutoff, shifted softplus, the SchNet featurisation, segmented sum / mean,
-    gather, ops.linear).  The routing is decided when the forward runs; the backward calls may
-    come after the block has exited.  Nests; restores the previous state on exit."""
+    gather, ops.linear) and, for a DimeNetPPModel with twice_differentiable=True, on the
+    DimeNet++ path (K11 geometry, K18d bases and projection, K19d).  The routing is decided when
+    the forward runs; the backward calls may come after the block has exited.  Nests; restores
+    the previous state on exit."""
 
     def __enter__(self):
         if compiling():
@@ -1643,6 +1645,227 @@ class TripletInteract1Fn(torch.autograd.Function):
         gS, gW = tops.triplet_interact1_bwd(gm, xd, S, W, idx_kj, offsets)
         gxd = _interact_grad_xd(ctx, tops.triplet_interact1_fwd, gm, xd, (S, W), idx_kj, idx_ji)
         return gxd, gS, gW, None, None, None
+
+
+# ------------------------------------------------- DimeNet++, twice differentiable (second_order)
+# Energy-and-force training differentiates F = -dE/dpos once more.  Each Function below has the
+# forward of its once-differentiable namesake and a backward that is itself a recorded Function
+# (*BwdFn), whose backward calls the *_bwd2 kernel and is once-differentiable: exactly two
+# orders.  As for CFConv, every Function saves the tensors it was GIVEN.
+class DimeEdgeBasis2Fn(torch.autograd.Function):
+    """DimeEdgeBasisFn whose backward is recorded (DimeEdgeBasisBwdFn)."""
+
+    @staticmethod
+    def forward(ctx, dist, freq, zeros, norm, cutoff, envelope_exponent):
+        _need_cuda(dist, freq, zeros, norm)
+        ctx.save_for_backward(dist, freq, zeros, norm)
+        ctx.cutoff, ctx.p = float(cutoff), int(envelope_exponent)
+        ctx.set_materialize_grads(False)
+        return _lib.torch_ops().dime_edge_basis_fwd(_f32c(dist), _f32c(freq), zeros, norm,
+                                                    ctx.cutoff, ctx.p)
+
+    @staticmethod
+    def backward(ctx, g_rbf, g_sbe):
+        dist, freq, zeros, norm = ctx.saved_tensors
+        if g_rbf is None and g_sbe is None:
+            return None, None, None, None, None, None
+        gd, gf = DimeEdgeBasisBwdFn.apply(dist, freq, zeros, norm, ctx.cutoff, ctx.p, g_rbf, g_sbe)
+        return gd, gf, None, None, None, None
+
+
+class DimeEdgeBasisBwdFn(torch.autograd.Function):
+    """(g_dist, g_freq) from the cotangents g_rbf / g_sbe (each may be None)
+    (gmp_dime_edge_basis_bwd_f32); backward by gmp_dime_edge_basis_bwd2_f32."""
+
+    @staticmethod
+    def forward(ctx, dist, freq, zeros, norm, cutoff, p, g_rbf, g_sbe):
+        ctx.save_for_backward(dist, freq, zeros, norm, g_rbf, g_sbe)
+        ctx.cutoff, ctx.p = cutoff, p
+        ctx.set_materialize_grads(False)
+        opt = [_f32c(t) if t is not None else None for t in (g_rbf, g_sbe)]
+        return _lib.torch_ops().dime_edge_basis_bwd(_f32c(dist), _f32c(freq), zeros, norm, cutoff,
+                                                    p, *opt)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, a_dist, a_freq):
+        dist, freq, zeros, norm, g_rbf, g_sbe = ctx.saved_tensors
+        if a_dist is None and a_freq is None:
+            return (None,) * 8
+        opt = [_f32c(t) if t is not None else None for t in (g_rbf, g_sbe, a_dist, a_freq)]
+        gg_rbf, gg_sbe, h_dist, h_freq = _lib.torch_ops().dime_edge_basis_bwd2(
+            _f32c(dist), _f32c(freq), zeros, norm, ctx.cutoff, ctx.p, *opt)
+        need = ctx.needs_input_grad
+        return (h_dist if need[0] else None, h_freq if need[1] else None, None, None, None, None,
+                gg_rbf if g_rbf is not None and need[6] else None,
+                gg_sbe if g_sbe is not None and need[7] else None)
+
+
+def dime_feature_major(weights, width):
+    """sph_feature_major from recorded torch ops: the (F, pad8(L b)) matrix stays connected to the
+    L weights, so the gradient of a force reaches them."""
+    L, b = len(weights), weights[0].shape[0]
+    w = torch.cat([x.t() for x in weights], dim=1)
+    if w.shape[0] != width:
+        raise ValueError(f"dime_feature_major: weights of width {w.shape[0]}, expected {width}")
+    pad = _pad8(L * b) - L * b
+    return torch.nn.functional.pad(w, (0, pad)) if pad else w.contiguous()
+
+
+def _sum_rows_per_edge(rows, idx_kj, like):
+    if rows.shape[0] == 0:
+        return torch.zeros_like(like, dtype=torch.float32)
+    return segment_reduce(rows, get_csr(idx_kj, like.shape[0]), "sum")[0]
+
+
+class DimeTripletProj2Fn(torch.autograd.Function):
+    """DimeTripletProjFn on the feature-major weights wt (dime_feature_major) returning the
+    stacked S (L, T, b); its backward is recorded (DimeTripletProjBwdFn)."""
+
+    @staticmethod
+    def forward(ctx, sbe, angle, wt, idx_kj, pref, n, k, L, b):
+        idx_kj = _i64c(idx_kj)
+        _need_cuda(sbe, angle, wt, idx_kj, pref)
+        ctx.save_for_backward(sbe, angle, wt, idx_kj, pref)
+        ctx.dims = (n, k, L, b)
+        return _lib.torch_ops().dime_triplet_proj_fwd(_f32c(sbe), _f32c(angle), idx_kj, pref,
+                                                      _f32c(wt), n, k, L, b)
+
+    @staticmethod
+    def backward(ctx, gS):
+        sbe, angle, wt, idx_kj, pref = ctx.saved_tensors
+        gw, gsbe, ga = DimeTripletProjBwdFn.apply(sbe, angle, wt, gS, idx_kj, pref, *ctx.dims)
+        return gsbe, ga, gw, None, None, None, None, None, None
+
+
+class DimeTripletProjBwdFn(torch.autograd.Function):
+    """(g_wt, g_sbe, g_angle) from gS (L, T, b) (gmp_dime_triplet_proj_bwd_f32 and the per-edge
+    sum over the CSR of idx_kj); backward by gmp_dime_triplet_proj_bwd2_f32."""
+
+    @staticmethod
+    def forward(ctx, sbe, angle, wt, gS, idx_kj, pref, n, k, L, b):
+        ctx.save_for_backward(sbe, angle, wt, gS, idx_kj, pref)
+        ctx.dims = (n, k, L, b)
+        ctx.set_materialize_grads(False)
+        gw, rows, ga = _lib.torch_ops().dime_triplet_proj_bwd(
+            _f32c(sbe), _f32c(angle), idx_kj, pref, _f32c(wt), n, k, L, b, _f32c(gS), True)
+        return gw, _sum_rows_per_edge(rows, idx_kj, sbe), ga
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, a_wt, a_sbe, a_angle):
+        sbe, angle, wt, gS, idx_kj, pref = ctx.saved_tensors
+        if a_wt is None and a_sbe is None and a_angle is None:
+            return (None,) * 10
+        opt = [_f32c(t) if t is not None else None for t in (a_sbe, a_angle, a_wt)]
+        need = ctx.needs_input_grad
+        geom = need[0] or need[1]
+        gg_S, h_wt, h_rows, h_angle = _lib.torch_ops().dime_triplet_proj_bwd2(
+            _f32c(sbe), _f32c(angle), idx_kj, pref, _f32c(wt), *ctx.dims, _f32c(gS), *opt, geom)
+        h_sbe = _sum_rows_per_edge(h_rows, idx_kj, sbe) if geom else None
+        return (h_sbe if need[0] else None, h_angle if need[1] else None,
+                h_wt if need[2] else None, gg_S if need[3] else None, None, None, None, None,
+                None, None)
+
+
+# K19d is one trilinear form F(gm, xd, S, W) = sum_t sum_c gm[ji_t, c] xd[kj_t, c] (W S_t)[c]:
+# dF/dgm is the message (TripletInteract1_2Fn), dF/dxd the same kernel over the CSR of idx_kj
+# (TripletInteract1GradXdFn), (dF/dS, dF/dW) the backward kernel (TripletInteract1BwdFn).  Every
+# second-order term is one of these with arguments substituted: composition, no new kernel.
+def _i1_msg(xd, S, W, idx_kj, offsets):
+    return _lib.torch_ops().triplet_interact1_fwd(_f32c(xd), _f32c(S), _f32c(W), idx_kj, None,
+                                                  offsets)
+
+
+def _i1_grad_xd(gm, S, W, idx_kj, idx_ji, n_edges):
+    if idx_kj.numel() == 0 or n_edges == 0:
+        return gm.new_zeros((n_edges, W.shape[0]), dtype=torch.float32)
+    csr = get_csr(idx_kj, n_edges)
+    return _lib.torch_ops().triplet_interact1_fwd(_f32c(gm), _f32c(S), _f32c(W), idx_ji, csr.perm,
+                                                  csr.rowptr)
+
+
+def _i1_bwd(gm, xd, S, W, idx_kj, offsets):
+    return _lib.torch_ops().triplet_interact1_bwd(_f32c(gm), _f32c(xd), _f32c(S), _f32c(W),
+                                                  idx_kj, offsets)
+
+
+def _add(a, b):
+    return b if a is None else (a if b is None else a + b)
+
+
+class TripletInteract1_2Fn(torch.autograd.Function):
+    """TripletInteract1Fn whose backward is recorded."""
+
+    @staticmethod
+    def forward(ctx, xd, S, W, idx_kj, idx_ji, offsets):
+        idx_kj, idx_ji, offsets = _i64c(idx_kj), _i64c(idx_ji), _i64c(offsets)
+        _need_cuda(xd, S, W, idx_kj, idx_ji, offsets)
+        ctx.save_for_backward(xd, S, W, idx_kj, idx_ji, offsets)
+        return _i1_msg(xd, S, W, idx_kj, offsets)
+
+    @staticmethod
+    def backward(ctx, a):
+        xd, S, W, idx_kj, idx_ji, offsets = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dxd = dS = dW = None
+        if need[0]:
+            dxd = TripletInteract1GradXdFn.apply(a, S, W, idx_kj, idx_ji, offsets)
+        if need[1] or need[2]:
+            dS, dW = TripletInteract1BwdFn.apply(a, xd, S, W, idx_kj, idx_ji, offsets)
+        return dxd, (dS if need[1] else None), (dW if need[2] else None), None, None, None
+
+
+class TripletInteract1GradXdFn(torch.autograd.Function):
+    """dF/dxd (E, I) from gm (E, I): the forward kernel over the CSR of idx_kj."""
+
+    @staticmethod
+    def forward(ctx, gm, S, W, idx_kj, idx_ji, offsets):
+        ctx.save_for_backward(gm, S, W, idx_kj, idx_ji, offsets)
+        return _i1_grad_xd(gm, S, W, idx_kj, idx_ji, offsets.numel() - 1)
+
+    @staticmethod
+    def backward(ctx, a):
+        gm, S, W, idx_kj, idx_ji, offsets = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dgm = dS = dW = None
+        if need[0]:
+            dgm = TripletInteract1_2Fn.apply(a, S, W, idx_kj, idx_ji, offsets)
+        if need[1] or need[2]:
+            dS, dW = TripletInteract1BwdFn.apply(gm, a, S, W, idx_kj, idx_ji, offsets)
+        return dgm, (dS if need[1] else None), (dW if need[2] else None), None, None, None
+
+
+class TripletInteract1BwdFn(torch.autograd.Function):
+    """(dF/dS (T, b), dF/dW (I, b)) from (gm, xd, S, W) (gmp_triplet_interact1_bwd_f32).  Its
+    backward reuses the two kernels with (a_S, W) and (S, a_W) substituted and is
+    once-differentiable."""
+
+    @staticmethod
+    def forward(ctx, gm, xd, S, W, idx_kj, idx_ji, offsets):
+        ctx.save_for_backward(gm, xd, S, W, idx_kj, idx_ji, offsets)
+        ctx.set_materialize_grads(False)
+        return _i1_bwd(gm, xd, S, W, idx_kj, offsets)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, a_S, a_W):
+        gm, xd, S, W, idx_kj, idx_ji, offsets = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        E = offsets.numel() - 1
+        dgm = dxd = dS = dW = None
+        for s_, w_ in ((a_S, W), (S, a_W)):
+            if s_ is None or w_ is None:
+                continue
+            if need[0]:
+                dgm = _add(dgm, _i1_msg(xd, s_, w_, idx_kj, offsets))
+            if need[1]:
+                dxd = _add(dxd, _i1_grad_xd(gm, s_, w_, idx_kj, idx_ji, E))
+        if a_S is not None and need[3]:
+            dW = _i1_bwd(gm, xd, a_S, W, idx_kj, offsets)[1]
+        if a_W is not None and need[2]:
+            dS = _i1_bwd(gm, xd, S, a_W, idx_kj, offsets)[0]
+        return dgm, dxd, dS, dW, None, None, None
 
 
 class FirstOrderOnlyFn(torch.autograd.Function):

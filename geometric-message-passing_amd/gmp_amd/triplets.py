@@ -112,8 +112,89 @@ class TripletGeomFn(torch.autograd.Function):
         return g_pos.to(pos.dtype), None, None, None, None
 
 
-def _geom(pos, edge_index, num_nodes, mode, use_torsion=False):
+class TripletGeom2Fn(torch.autograd.Function):
+    """TripletGeomFn (without torsion) whose backward is recorded (TripletGeomBwdFn), so that
+    d pos can be differentiated once more: energy-and-force training."""
+
+    @staticmethod
+    def forward(ctx, pos, edge_index, num_nodes, mode):
+        dist, angle, _, idx_kj, idx_ji = _run(pos, edge_index, num_nodes, mode, True, False, True)
+        ctx.save_for_backward(pos, ops._i64c(edge_index), idx_kj, idx_ji)
+        ctx.mode, ctx.n = mode, int(num_nodes)
+        ctx.mark_non_differentiable(idx_kj, idx_ji)
+        ctx.set_materialize_grads(False)
+        torsion = torch.empty(0, dtype=torch.float32, device=dist.device)
+        return dist, angle, torsion, idx_kj, idx_ji
+
+    @staticmethod
+    def backward(ctx, g_dist, g_angle, _g0, _g1, _g2):
+        pos, ei, idx_kj, idx_ji = ctx.saved_tensors
+        if not ctx.needs_input_grad[0] or (g_dist is None and g_angle is None):
+            return None, None, None, None
+        g_pos = TripletGeomBwdFn.apply(pos, ei, idx_kj, idx_ji, g_dist, g_angle, ctx.mode, ctx.n)
+        return g_pos, None, None, None
+
+
+def _geom_rows(n_rows, dev):
+    return (torch.empty((n_rows, 3), dtype=torch.float32, device=dev),
+            torch.empty(n_rows, dtype=torch.int64, device=dev))
+
+
+def _rows_to_pos(rows, node, n, dtype):
+    """The deterministic segmented sum of the gradient rows by node (zeros without rows)."""
+    if rows.shape[0] == 0:
+        return torch.zeros((n, 3), dtype=dtype, device=rows.device)
+    return ops.segment_reduce(rows, ops.CSR(node, n), "sum")[0].to(dtype)
+
+
+class TripletGeomBwdFn(torch.autograd.Function):
+    """d pos (N, 3) from pos and the cotangents g_dist (E) / g_angle (T), each possibly None
+    (gmp_triplet_geom_bwd_f32 and the segmented sum by node); backward by
+    gmp_triplet_geom_bwd2_f32.  The tensors given are saved as they are (a copy made here would
+    be cut off from the graph).  The second backward is once-differentiable."""
+
+    @staticmethod
+    def forward(ctx, pos, ei, idx_kj, idx_ji, g_dist, g_angle, mode, n):
+        ctx.save_for_backward(pos, ei, idx_kj, idx_ji, g_dist, g_angle)
+        ctx.mode, ctx.n = mode, n
+        E, T = ei.shape[1], idx_kj.numel()
+        rows, node = _geom_rows(3 * T + 2 * E, pos.device)
+        gd = ops._f32c(g_dist) if g_dist is not None else None
+        ga = ops._f32c(g_angle) if g_angle is not None else None
+        p32 = ops._f32c(pos)
+        ops.check(_lib.load().gmp_triplet_geom_bwd_f32(
+            ops._p(p32), ops._p(ei), E, ops._p(idx_kj), ops._p(idx_ji), T, mode, ops._p(gd),
+            ops._p(ga), ops._p(rows), ops._p(node), ops._stream()), "gmp_triplet_geom_bwd_f32")
+        return _rows_to_pos(rows, node, n, pos.dtype)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, a_pos):
+        pos, ei, idx_kj, idx_ji, g_dist, g_angle = ctx.saved_tensors
+        E, T = ei.shape[1], idx_kj.numel()
+        dev = pos.device
+        need = ctx.needs_input_grad
+        rows, node = _geom_rows(3 * T + 2 * E, dev)
+        gg_d = torch.empty(E, dtype=torch.float32, device=dev)
+        gg_a = torch.empty(T, dtype=torch.float32, device=dev)
+        gd = ops._f32c(g_dist) if g_dist is not None else None
+        ga = ops._f32c(g_angle) if g_angle is not None else None
+        p32, a32 = ops._f32c(pos), ops._f32c(a_pos)
+        ops.check(_lib.load().gmp_triplet_geom_bwd2_f32(
+            ops._p(p32), ops._p(ei), E, ops._p(idx_kj), ops._p(idx_ji), T, ctx.mode, ops._p(gd),
+            ops._p(ga), ops._p(a32), ops._p(gg_d), ops._p(gg_a), ops._p(rows), ops._p(node),
+            ops._stream()), "gmp_triplet_geom_bwd2_f32")
+        h_pos = _rows_to_pos(rows, node, ctx.n, pos.dtype) if need[0] else None
+        return (h_pos, None, None, None, gg_d if g_dist is not None and need[4] else None,
+                gg_a if g_angle is not None and need[5] else None, None, None)
+
+
+def _geom(pos, edge_index, num_nodes, mode, use_torsion=False, twice=False):
     if pos.requires_grad and torch.is_grad_enabled():
+        if twice:
+            if use_torsion:
+                raise NotImplementedError("the torsion has no second-order backward")
+            return TripletGeom2Fn.apply(pos, edge_index, num_nodes, mode)
         return TripletGeomFn.apply(pos, edge_index, num_nodes, mode, use_torsion)
     return _run(pos, edge_index, num_nodes, mode, True, use_torsion, True)
 
@@ -137,10 +218,12 @@ def dimenet_triplets(edge_index, num_nodes):
     return col, row, col[idx_ji], row[idx_ji], row[idx_kj], idx_kj, idx_ji
 
 
-def dimenet_angles(pos, edge_index, num_nodes):
+def dimenet_angles(pos, edge_index, num_nodes, twice_differentiable=False):
     """dimenet.py:79-90: -> dist (E), angle (T, vertex i), i, j, idx_i, idx_j, idx_k, idx_kj,
-    idx_ji."""
-    dist, angle, _, idx_kj, idx_ji = _geom(pos, edge_index, num_nodes, 1)
+    idx_ji.  With twice_differentiable the backward to pos is recorded (TripletGeom2Fn), so a
+    force can be differentiated again."""
+    dist, angle, _, idx_kj, idx_ji = _geom(pos, edge_index, num_nodes, 1,
+                                           twice=twice_differentiable)
     row, col = edge_index
     return (dist, angle, col, row, col[idx_ji], row[idx_ji], row[idx_kj], idx_kj, idx_ji)
 

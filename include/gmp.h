@@ -879,6 +879,19 @@ int gmp_triplet_geom_bwd_f32(const float* pos, const int64_t* edge_index, int64_
                              const int64_t* idx_kj, const int64_t* idx_ji, int64_t n_triplets,
                              int mode, const float* grad_dist, const float* grad_angle,
                              float* rows, int64_t* node, void* stream);
+/* Second backward of dist and angle (models/dimenet.py:82-89 differentiated twice: a loss on the
+ * forces -dE/dpos), modes 0 and 1, no torsion.  a_pos (N, 3) is the cotangent of the first
+ * backward's d pos.  Writes gg_dist (E) = (a_i - a_j).(p_i - p_j) / d and gg_angle (T) =
+ * a_u.dtheta/du + a_v.dtheta/dv (the gradients w.r.t. grad_dist / grad_angle; either may be
+ * NULL), and 3T + 2E rows with node ids in the layout of gmp_triplet_geom_bwd_f32: the
+ * directional derivative along a of the rows that entry writes; their segmented sum by node is
+ * the gradient w.r.t. pos.  grad_dist / grad_angle may be NULL (zero rows).  A collinear
+ * triplet, a zero-length edge and a zero cotangent follow the first backward. */
+int gmp_triplet_geom_bwd2_f32(const float* pos, const int64_t* edge_index, int64_t n_edges,
+                              const int64_t* idx_kj, const int64_t* idx_ji, int64_t n_triplets,
+                              int mode, const float* grad_dist, const float* grad_angle,
+                              const float* a_pos, float* gg_dist, float* gg_angle, float* rows,
+                              int64_t* node, void* stream);
 /* Backward of the SphereNet torsion (spherenet_layer.py:535-559 under autograd) w.r.t. pos:
  * torsion_kn (T, from gmp_triplet_fill_f32; -1 = no candidate) is the scatter-min's winning
  * k_n, which alone receives the gradient (torch_scatter's arg routing).  Writes 4T rows of 3
@@ -1143,6 +1156,39 @@ int gmp_dime_triplet_proj_bwd_f32(int64_t n_triplets, int64_t n_edges, int num_s
                                   int n_layers, int b, const float* grad_S, float* grad_w,
                                   float* partials, float* grad_sbe_rows, float* grad_angle,
                                   void* stream);
+
+/* Second backwards of K18d (a loss on the forces differentiates PyG's BesselBasisLayer /
+ * SphericalBasisLayer, models/dimenet.py:86-90, twice).  Additions only.
+ *
+ * Edge basis: the first backward maps (grad_rbf, grad_sbe) to (grad_dist, grad_freq); a_dist (E)
+ * and a_freq (k) are the cotangents of those (each may be NULL, as may grad_rbf / grad_sbe).
+ * Writes gg_rbf (E, k), gg_sbe (E, n k) (the gradients w.r.t. grad_rbf / grad_sbe), h_dist (E)
+ * and h_freq (k) (w.r.t. dist / freq; h_freq through gmp_dime_edge_basis_bwd2_partial_rows(E)
+ * ordered partial rows of k).  Double arithmetic rounded once; an edge with x >= 1 gives exact
+ * zeros in all four.
+ *
+ * Triplet projection: the first backward maps grad_S (L, T, b) to (grad_w, grad_sbe, grad_angle);
+ * a_w_t (n k, ld, feature-major as w_sbf1_t), a_sbe (E, n k), a_angle (T) are their cotangents
+ * (each may be NULL).  Writes gg_S (L, T, b), h_w (n k, ld) through partials
+ * (gmp_dime_triplet_proj_bwd2_partial_rows(T) rows of n k ld) and, if given (both or neither),
+ * h_sbe_rows (T, n k) (summed per edge by the caller over the CSR of idx_kj) and h_angle (T).
+ * Up to three kernels; no atomics.  T = 0: GMP_OK and a zero h_w. */
+int64_t gmp_dime_edge_basis_bwd2_partial_rows(int64_t n_edges);
+int gmp_dime_edge_basis_bwd2_f32(const float* dist, int64_t n_edges, float cutoff,
+                                 int envelope_exponent, const float* freq, int num_radial,
+                                 const float* zeros, const float* norm, int num_spherical,
+                                 const float* grad_rbf, const float* grad_sbe,
+                                 const float* a_dist, const float* a_freq, float* gg_rbf,
+                                 float* gg_sbe, float* h_dist, float* h_freq,
+                                 float* freq_partials, void* stream);
+int64_t gmp_dime_triplet_proj_bwd2_partial_rows(int64_t n_triplets);
+int gmp_dime_triplet_proj_bwd2_f32(int64_t n_triplets, int64_t n_edges, int num_spherical,
+                                   int num_radial, const float* sbe, const float* angle,
+                                   const int64_t* idx_kj, const float* pref,
+                                   const float* w_sbf1_t, int n_layers, int b,
+                                   const float* grad_S, const float* a_sbe, const float* a_angle,
+                                   const float* a_w_t, float* gg_S, float* h_w, float* partials,
+                                   float* h_sbe_rows, float* h_angle, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * K19d DimeNet++ triplet interaction of one layer (InteractionPPBlock), K19 with one factor:
