@@ -16,62 +16,12 @@
 // for k_n = k plane1 == plane2, and the sign of the contracted cross product's rounding
 // residual decides whether that candidate's torsion is ~1e-9 or 2*pi — the reference's
 // output depends on it, so the kernel follows it.
-#include "gmp_common.h"
+#include "gmp_triplet_geom.h"
 
 namespace gmp {
 namespace {
 
 constexpr float kTwoPi = 6.283185307179586f;
-
-struct V3 {
-  float x, y, z;
-};
-
-__device__ __forceinline__ V3 ld3(const float* __restrict__ p, int64_t a) {
-  return V3{p[3 * a], p[3 * a + 1], p[3 * a + 2]};
-}
-__device__ __forceinline__ V3 sub3(V3 a, V3 b) {
-  return V3{__fsub_rn(a.x, b.x), __fsub_rn(a.y, b.y), __fsub_rn(a.z, b.z)};
-}
-// torch.cross on CPU: fma(a_i, b_j, -(a_j * b_i))
-__device__ __forceinline__ V3 cross3(V3 a, V3 b) {
-  return V3{__fmaf_rn(a.y, b.z, -__fmul_rn(a.z, b.y)), __fmaf_rn(a.z, b.x, -__fmul_rn(a.x, b.z)),
-            __fmaf_rn(a.x, b.y, -__fmul_rn(a.y, b.x))};
-}
-// (a * b).sum(-1): the reduction starts from +0, so an all-(-0) sum is +0 (atan2(0, +0) = 0,
-// not pi, for a degenerate self-loop vector)
-__device__ __forceinline__ float dot3(V3 a, V3 b) {
-  return __fadd_rn(__fadd_rn(__fadd_rn(0.f, __fmul_rn(a.x, b.x)), __fmul_rn(a.y, b.y)),
-                   __fmul_rn(a.z, b.z));
-}
-// a.norm(dim=-1)
-__device__ __forceinline__ float norm3(V3 a) {
-  float acc = __fmul_rn(a.x, a.x);
-  acc = __fmaf_rn(a.y, a.y, acc);
-  acc = __fmaf_rn(a.z, a.z, acc);
-  return __fsqrt_rn(acc);
-}
-// a.pow(2).sum(-1).sqrt()
-__device__ __forceinline__ float len3(V3 a) { return __fsqrt_rn(dot3(a, a)); }
-
-// [p, q): entries of the (source-sorted) adjacency row [r0, r1) whose source equals s
-__device__ __forceinline__ void equal_range(const int64_t* __restrict__ asrc, int64_t r0,
-                                            int64_t r1, int64_t s, int64_t& p, int64_t& q) {
-  int64_t lo = r0, hi = r1;
-  while (lo < hi) {
-    const int64_t m = (lo + hi) >> 1;
-    if (asrc[m] < s) lo = m + 1;
-    else hi = m;
-  }
-  p = lo;
-  hi = r1;
-  while (lo < hi) {
-    const int64_t m = (lo + hi) >> 1;
-    if (asrc[m] <= s) lo = m + 1;
-    else hi = m;
-  }
-  q = lo;
-}
 
 __global__ void triplet_count_kernel(const float* __restrict__ pos,
                                      const int64_t* __restrict__ ei, int64_t E,
@@ -179,12 +129,6 @@ __global__ __launch_bounds__(kFB) void triplet_fill_kernel(
   }
 }
 
-int grid_for(int64_t n) {
-  int64_t g = ceil_div(n, 256);
-  const int64_t cap = (int64_t)device_cu_count() * 16;
-  return (int)(g > cap ? cap : (g < 1 ? 1 : g));
-}
-
 // Backward of dist and angle w.r.t. pos (dimenet.py:82-89 / spherenet_layer.py:509,531-535
 // under autograd).  theta = atan2(b, a), a = u.v, b = |c|, c = u x v:
 //   d theta = (a db - b da) / (a^2 + b^2);  da/du = v, da/dv = u;
@@ -207,31 +151,14 @@ __global__ void triplet_geom_bwd_kernel(const float* __restrict__ pos,
       const int64_t j = ei[e], i = ei[E + e], k = ei[idx_kj[t]];
       const int64_t vtx = mode == 0 ? j : i, ue = mode == 0 ? i : j;
       const V3 pv = ld3(pos, vtx), u = sub3(ld3(pos, ue), pv), v = sub3(ld3(pos, k), pv);
-      float gux = 0.f, guy = 0.f, guz = 0.f, gvx = 0.f, gvy = 0.f, gvz = 0.f;
-      const float g = g_angle ? g_angle[t] : 0.f;
-      if (g != 0.f) {
-        const V3 c = cross3(u, v);
-        const float b = norm3(c), a = dot3(u, v);
-        const float den = a * a + b * b;
-        const float ga = -g * b / den, gb = g * a / den;
-        gux = ga * v.x; guy = ga * v.y; guz = ga * v.z;
-        gvx = ga * u.x; gvy = ga * u.y; gvz = ga * u.z;
-        if (b > 0.f) {
-          const V3 ch{c.x / b, c.y / b, c.z / b};
-          gux += gb * (v.y * ch.z - v.z * ch.y);
-          guy += gb * (v.z * ch.x - v.x * ch.z);
-          guz += gb * (v.x * ch.y - v.y * ch.x);
-          gvx += gb * (ch.y * u.z - ch.z * u.y);
-          gvy += gb * (ch.z * u.x - ch.x * u.z);
-          gvz += gb * (ch.x * u.y - ch.y * u.x);
-        }
-      }
+      V3 gu, gv;
+      angle_bwd(u, v, g_angle ? g_angle[t] : 0.f, gu, gv);
       float* r0 = rows + 3 * t;
       float* r1 = rows + 3 * (T + t);
       float* r2 = rows + 3 * (2 * T + t);
-      r0[0] = -(gux + gvx); r0[1] = -(guy + gvy); r0[2] = -(guz + gvz);
-      r1[0] = gux; r1[1] = guy; r1[2] = guz;
-      r2[0] = gvx; r2[1] = gvy; r2[2] = gvz;
+      r0[0] = -(gu.x + gv.x); r0[1] = -(gu.y + gv.y); r0[2] = -(gu.z + gv.z);
+      r1[0] = gu.x; r1[1] = gu.y; r1[2] = gu.z;
+      r2[0] = gv.x; r2[1] = gv.y; r2[2] = gv.z;
       node[t] = vtx;
       node[T + t] = ue;
       node[2 * T + t] = k;
@@ -264,20 +191,6 @@ __global__ void triplet_geom_bwd_kernel(const float* __restrict__ pos,
 // there, the rest runs in double and is rounded once (second derivatives divide by b^2, d^2).
 // Dead cases as the first backward: b = 0 drops the c^ terms and their tangents, len = 0 and
 // g == 0 write zero rows (gg_* is still written).
-struct D3 {
-  double x, y, z;
-};
-__device__ __forceinline__ D3 dd3(V3 a) { return D3{(double)a.x, (double)a.y, (double)a.z}; }
-__device__ __forceinline__ D3 dxf(D3 a, D3 b) {
-  return D3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-}
-__device__ __forceinline__ double ddot(D3 a, D3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ D3 dadd(D3 a, D3 b) { return D3{a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ D3 dscale(double s, D3 a) { return D3{s * a.x, s * a.y, s * a.z}; }
-__device__ __forceinline__ void st3(float* r, D3 a) {
-  r[0] = (float)a.x; r[1] = (float)a.y; r[2] = (float)a.z;
-}
-
 __global__ void triplet_geom_bwd2_kernel(const float* __restrict__ pos,
                                          const int64_t* __restrict__ ei, int64_t E,
                                          const int64_t* __restrict__ idx_kj,
@@ -299,32 +212,8 @@ __global__ void triplet_geom_bwd2_kernel(const float* __restrict__ pos,
       const D3 u = dd3(sub3(ld3(pos, ue), pv)), v = dd3(sub3(ld3(pos, k), pv));
       const D3 du = dd3(sub3(ld3(a_pos, ue), av)), dv = dd3(sub3(ld3(a_pos, k), av));
       const double g = g_angle ? (double)g_angle[t] : 0.0;
-      const D3 c = dxf(u, v), dc = dadd(dxf(du, v), dxf(u, dv));
-      const double b = sqrt(ddot(c, c)), a = ddot(u, v);
-      const double da = ddot(du, v) + ddot(u, dv);
-      const double db = b > 0.0 ? ddot(c, dc) / b : 0.0;
-      const double den = a * a + b * b;
-      D3 hu{0.0, 0.0, 0.0}, hv{0.0, 0.0, 0.0};
-      double gg = 0.0;
-      if (den > 0.0) {
-        gg = (a * db - b * da) / den;
-        if (g != 0.0) {
-          const double dden = 2.0 * (a * da + b * db);
-          const double ga = -g * b / den, gb = g * a / den;
-          const double dga = -g * (db / den - b * dden / (den * den));
-          const double dgb = g * (da / den - a * dden / (den * den));
-          hu = dadd(dscale(dga, v), dscale(ga, dv));
-          hv = dadd(dscale(dga, u), dscale(ga, du));
-          if (b > 0.0) {
-            const D3 ch = dscale(1.0 / b, c);
-            const D3 dch = dadd(dscale(1.0 / b, dc), dscale(-db / (b * b), c));
-            hu = dadd(hu, dadd(dscale(dgb, dxf(v, ch)),
-                               dscale(gb, dadd(dxf(dv, ch), dxf(v, dch)))));
-            hv = dadd(hv, dadd(dscale(dgb, dxf(ch, u)),
-                               dscale(gb, dadd(dxf(dch, u), dxf(ch, du)))));
-          }
-        }
-      }
+      D3 hu, hv;
+      const double gg = angle_bwd2(u, v, du, dv, g, hu, hv);
       if (gg_angle) gg_angle[t] = (float)gg;
       st3(rows + 3 * t, dscale(-1.0, dadd(hu, hv)));
       st3(rows + 3 * (T + t), hu);
@@ -425,7 +314,7 @@ int gmp_triplet_count(const float* pos, const int64_t* edge_index, int64_t n_edg
   GMP_CHECK_ARG(n_edges >= 0 && n_nodes >= 0);
   if (n_edges == 0) return GMP_OK;
   GMP_CHECK_ARG(edge_index && adj_rowptr && adj_src && counts && (pos || !dist));
-  triplet_count_kernel<<<grid_for(n_edges), 256, 0, as_stream(stream)>>>(
+  triplet_count_kernel<<<triplet_grid_for(n_edges), 256, 0, as_stream(stream)>>>(
       pos, edge_index, n_edges, adj_rowptr, adj_src, counts, dist);
   return launch_status();
 }
@@ -454,7 +343,7 @@ int gmp_triplet_geom_bwd_f32(const float* pos, const int64_t* edge_index, int64_
   GMP_CHECK_ARG(n_edges >= 0 && n_triplets >= 0 && (mode == 0 || mode == 1));
   if (n_edges + n_triplets == 0) return GMP_OK;
   GMP_CHECK_ARG(pos && edge_index && rows && node && (n_triplets == 0 || (idx_kj && idx_ji)));
-  triplet_geom_bwd_kernel<<<grid_for(n_edges + n_triplets), 256, 0, as_stream(stream)>>>(
+  triplet_geom_bwd_kernel<<<triplet_grid_for(n_edges + n_triplets), 256, 0, as_stream(stream)>>>(
       pos, edge_index, n_edges, idx_kj, idx_ji, n_triplets, mode, grad_dist, grad_angle, rows,
       node);
   return launch_status();
@@ -469,7 +358,7 @@ int gmp_triplet_geom_bwd2_f32(const float* pos, const int64_t* edge_index, int64
   if (n_edges + n_triplets == 0) return GMP_OK;
   GMP_CHECK_ARG(pos && a_pos && edge_index && rows && node &&
                 (n_triplets == 0 || (idx_kj && idx_ji)));
-  triplet_geom_bwd2_kernel<<<grid_for(n_edges + n_triplets), 256, 0, as_stream(stream)>>>(
+  triplet_geom_bwd2_kernel<<<triplet_grid_for(n_edges + n_triplets), 256, 0, as_stream(stream)>>>(
       pos, edge_index, n_edges, idx_kj, idx_ji, n_triplets, mode, grad_dist, grad_angle, a_pos,
       gg_dist, gg_angle, rows, node);
   return launch_status();
@@ -484,7 +373,7 @@ int gmp_triplet_torsion_bwd_f32(const float* pos, const int64_t* edge_index, int
   if (n_triplets == 0) return GMP_OK;
   GMP_CHECK_ARG(pos && edge_index && idx_kj && idx_ji && torsion_kn && grad_torsion && rows &&
                 node);
-  triplet_torsion_bwd_kernel<<<grid_for(n_triplets), 256, 0, as_stream(stream)>>>(
+  triplet_torsion_bwd_kernel<<<triplet_grid_for(n_triplets), 256, 0, as_stream(stream)>>>(
       pos, edge_index, n_edges, idx_kj, idx_ji, torsion_kn, n_triplets, grad_torsion, rows, node);
   return launch_status();
 }

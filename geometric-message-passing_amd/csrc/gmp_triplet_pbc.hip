@@ -1,0 +1,267 @@
+// K11p: DimeNet's triplets and angles on a periodic graph (the contract is stated in
+// include/gmp.h next to K11).  An edge is e = (j -> i, S_e) with the K9p vector
+// vec_e = (pos[j] - pos[i]) + t_e; its triplets are the entries kj = (k -> j, S_kj) of j's
+// in-adjacency except the reverse images of e (k == i and S_kj == -S_e, an integer compare);
+//   dist[e] = len3(vec_e),  angle[t] = atan2(|u x v|, u.v),  u = vec_ji, v = u + vec_kj
+// (v: the image of k relative to i).  The geometry is a function of the per-edge vectors only,
+// so the backward kernels work in edge-vector form: they take vec (E, 3) and write per-triplet
+// and per-edge rows that are summed per edge over CSRs the model already holds (no node[] array,
+// no sort per backward); pos and cell are reached through the linear maps vec = P pos + t.
+// The per-triplet arithmetic is gmp_triplet_geom.h's, shared with the node-form kernels.
+#include "gmp_triplet_geom.h"
+
+namespace gmp {
+namespace {
+
+struct I3 {
+  int x, y, z;
+};
+__device__ __forceinline__ I3 ldi3(const int32_t* __restrict__ p, int64_t a) {
+  return I3{p[3 * a], p[3 * a + 1], p[3 * a + 2]};
+}
+// the entry's shift is the negative of s (s of the edge whose reverse image is excluded)
+__device__ __forceinline__ bool is_neg(I3 a, I3 s) {
+  return a.x == -s.x && a.y == -s.y && a.z == -s.z;
+}
+
+// |d| with the rounding of K11's dist as triplet_count_kernel is compiled (its dot3 contracts to
+// fma(y, y, x x) + z z), pinned here so that a graph with all shifts zero reproduces K11's dist
+// bit for bit whatever the compiler makes of this kernel's schedule.
+__device__ __forceinline__ float len3_k11(V3 a) {
+#pragma clang fp contract(off)
+  const float xx = a.x * a.x, zz = a.z * a.z;
+  return __fsqrt_rn(__builtin_fmaf(a.y, a.y, xx) + zz);
+}
+
+// counts[e] = in-degree(j) - #{entries (i -> j, -S_e)}: equal_range on source i, then a scan of
+// that run (the images of i around j: short) for the reverse images.
+__global__ void triplet_count_pbc_kernel(const float* __restrict__ vec,
+                                         const int64_t* __restrict__ ei, int64_t E,
+                                         const int64_t* __restrict__ arow,
+                                         const int64_t* __restrict__ asrc,
+                                         const int64_t* __restrict__ aeid,
+                                         const int32_t* __restrict__ sidx,
+                                         int64_t* __restrict__ counts,
+                                         float* __restrict__ dist) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < E; e += stride) {
+    const int64_t j = ei[e], i = ei[E + e];
+    const int64_t r0 = arow[j], r1 = arow[j + 1];
+    int64_t p, q;
+    equal_range(asrc, r0, r1, i, p, q);
+    const I3 s = ldi3(sidx, e);
+    int64_t excluded = 0;
+    for (int64_t m = p; m < q; ++m) excluded += is_neg(ldi3(sidx, aeid[m]), s) ? 1 : 0;
+    counts[e] = (r1 - r0) - excluded;
+    if (dist) dist[e] = len3_k11(ld3(vec, e));
+  }
+}
+
+// The two phases of triplet_fill_kernel (a workgroup per block of kFBp edges: the edge windows
+// staged in LDS, then the block's triplets spread over the threads).  The excluded entries are
+// no longer one contiguous run: a triplet whose slot falls at or after the start p of the run of
+// source i walks the run and skips the reverse images; past the run nothing is excluded.
+constexpr int kFBp = 256;
+
+__global__ __launch_bounds__(kFBp) void triplet_fill_pbc_kernel(
+    const float* __restrict__ vec, const int64_t* __restrict__ ei, int64_t E,
+    const int64_t* __restrict__ arow, const int64_t* __restrict__ asrc,
+    const int64_t* __restrict__ aeid, const int32_t* __restrict__ sidx,
+    const int64_t* __restrict__ offs, int64_t* __restrict__ idx_kj,
+    int64_t* __restrict__ idx_ji, float* __restrict__ angle) {
+  __shared__ int64_t s_off[kFBp + 1];
+  __shared__ int64_t s_r0[kFBp], s_r1[kFBp], s_p[kFBp], s_q[kFBp];
+  __shared__ int s_sx[kFBp], s_sy[kFBp], s_sz[kFBp];
+  const int64_t e0 = (int64_t)blockIdx.x * kFBp;
+  const int nE = (int)(E - e0 < kFBp ? E - e0 : kFBp);
+  const int tid = threadIdx.x;
+  if (tid < nE) {
+    const int64_t e = e0 + tid;
+    const int64_t j = ei[e], i = ei[E + e];
+    const int64_t r0 = arow[j], r1 = arow[j + 1];
+    int64_t p, q;
+    equal_range(asrc, r0, r1, i, p, q);
+    const I3 s = ldi3(sidx, e);
+    s_off[tid] = offs[e];
+    s_r0[tid] = r0;
+    s_r1[tid] = r1;
+    s_p[tid] = p;
+    s_q[tid] = q;
+    s_sx[tid] = s.x;
+    s_sy[tid] = s.y;
+    s_sz[tid] = s.z;
+  }
+  if (tid == 0) s_off[nE] = offs[e0 + nE];
+  __syncthreads();
+  const int64_t t_begin = s_off[0], t_end = s_off[nE];
+  for (int64_t t = t_begin + tid; t < t_end; t += kFBp) {
+    int lo = 0, hi = nE;  // largest local edge with s_off <= t
+    while (hi - lo > 1) {
+      const int m = (lo + hi) >> 1;
+      if (s_off[m] <= t) lo = m;
+      else hi = m;
+    }
+    const int64_t e = e0 + lo;
+    const int64_t r0 = s_r0[lo], r1 = s_r1[lo], p = s_p[lo], q = s_q[lo];
+    int64_t slot = r0 + (t - s_off[lo]);
+    if (slot >= p) {
+      const I3 s{s_sx[lo], s_sy[lo], s_sz[lo]};
+      int64_t rem = slot - p, m = p;  // the rem-th kept entry at or after p
+      for (; m < q; ++m) {
+        if (is_neg(ldi3(sidx, aeid[m]), s)) continue;
+        if (rem == 0) break;
+        --rem;
+      }
+      slot = m + rem;
+    }
+    if (slot >= r1) slot = r1 > r0 ? r1 - 1 : 0;  // offsets that disagree with the count
+    const int64_t kj = aeid[slot];
+    idx_kj[t] = kj;
+    idx_ji[t] = e;
+    if (angle) {
+      const V3 u = ld3(vec, e), v = add3(u, ld3(vec, kj));
+      angle[t] = atan2f(norm3(cross3(u, v)), dot3(u, v));
+    }
+  }
+}
+
+// First backward in edge-vector form.  rows (2T + E, 3): [0, T) g_u + g_v, the share of edge
+// idx_ji[t] (u and v both carry vec_ji); [T, 2T) g_v, the share of edge idx_kj[t];
+// [2T, 2T + E) g_dist vec / d.  The caller sums [0, T) over the triplet offsets, [T, 2T) over the
+// CSR of idx_kj and adds [2T, 2T + E): deterministic, no atomics.
+__global__ void triplet_vec_bwd_kernel(const float* __restrict__ vec, int64_t E,
+                                       const int64_t* __restrict__ idx_kj,
+                                       const int64_t* __restrict__ idx_ji, int64_t T,
+                                       const float* __restrict__ g_dist,
+                                       const float* __restrict__ g_angle,
+                                       float* __restrict__ rows) {
+  const int64_t n = T + E;
+  for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < n;
+       q += (int64_t)gridDim.x * blockDim.x) {
+    if (q < T) {
+      const int64_t t = q;
+      const V3 u = ld3(vec, idx_ji[t]), v = add3(u, ld3(vec, idx_kj[t]));
+      V3 gu, gv;
+      angle_bwd(u, v, g_angle ? g_angle[t] : 0.f, gu, gv);
+      float* r0 = rows + 3 * t;
+      float* r1 = rows + 3 * (T + t);
+      r0[0] = gu.x + gv.x; r0[1] = gu.y + gv.y; r0[2] = gu.z + gv.z;
+      r1[0] = gv.x; r1[1] = gv.y; r1[2] = gv.z;
+    } else {
+      const int64_t e = q - T;
+      const V3 d = ld3(vec, e);
+      const float len = len3(d);
+      const float g = g_dist ? g_dist[e] : 0.f;
+      const float s = (g != 0.f && len > 0.f) ? g / len : 0.f;
+      float* r = rows + 3 * (2 * T + e);
+      r[0] = s * d.x; r[1] = s * d.y; r[2] = s * d.z;
+    }
+  }
+}
+
+// Second backward in edge-vector form: with the cotangent a_vec (E, 3) of the first backward's
+// g_vec, a_u = a_vec[ji] and a_v = a_vec[ji] + a_vec[kj] (fp32, as u and v),
+//   gg_dist[e] = a_vec_e . vec_e / d,  gg_angle[t] = a_u.dtheta/du + a_v.dtheta/dv,
+//   rows: the directional derivative along a_vec of the rows triplet_vec_bwd_kernel writes, in
+//   its layout.  Conventions of triplet_geom_bwd2_kernel: everything after u, v, a_u, a_v in
+//   double, rounded once; the dead cases of the first backward.
+__global__ void triplet_vec_bwd2_kernel(const float* __restrict__ vec, int64_t E,
+                                        const int64_t* __restrict__ idx_kj,
+                                        const int64_t* __restrict__ idx_ji, int64_t T,
+                                        const float* __restrict__ g_dist,
+                                        const float* __restrict__ g_angle,
+                                        const float* __restrict__ a_vec,
+                                        float* __restrict__ gg_dist,
+                                        float* __restrict__ gg_angle,
+                                        float* __restrict__ rows) {
+  const int64_t n = T + E;
+  for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < n;
+       q += (int64_t)gridDim.x * blockDim.x) {
+    if (q < T) {
+      const int64_t t = q, ji = idx_ji[t], kj = idx_kj[t];
+      const V3 u32 = ld3(vec, ji), a32 = ld3(a_vec, ji);
+      const D3 u = dd3(u32), v = dd3(add3(u32, ld3(vec, kj)));
+      const D3 du = dd3(a32), dv = dd3(add3(a32, ld3(a_vec, kj)));
+      const double g = g_angle ? (double)g_angle[t] : 0.0;
+      D3 hu, hv;
+      const double gg = angle_bwd2(u, v, du, dv, g, hu, hv);
+      if (gg_angle) gg_angle[t] = (float)gg;
+      st3(rows + 3 * t, dadd(hu, hv));
+      st3(rows + 3 * (T + t), hv);
+    } else {
+      const int64_t e = q - T;
+      const D3 d = dd3(ld3(vec, e)), dd = dd3(ld3(a_vec, e));
+      const double len = sqrt(ddot(d, d));
+      const double g = g_dist ? (double)g_dist[e] : 0.0;
+      const double dlen = len > 0.0 ? ddot(d, dd) / len : 0.0;
+      D3 h{0.0, 0.0, 0.0};
+      if (g != 0.0 && len > 0.0)
+        h = dadd(dscale(g / len, dd), dscale(-g * dlen / (len * len), d));
+      if (gg_dist) gg_dist[e] = (float)dlen;
+      st3(rows + 3 * (2 * T + e), h);
+    }
+  }
+}
+
+}  // namespace
+}  // namespace gmp
+
+using namespace gmp;
+
+extern "C" {
+
+int gmp_triplet_count_pbc(const float* vec, const int64_t* edge_index, int64_t n_edges,
+                          int64_t n_nodes, const int64_t* adj_rowptr, const int64_t* adj_src,
+                          const int64_t* adj_eid, const int32_t* shift_idx, int64_t* counts,
+                          float* dist, void* stream) {
+  GMP_CHECK_ARG(n_edges >= 0 && n_nodes >= 0);
+  if (n_edges == 0) return GMP_OK;
+  GMP_CHECK_ARG(edge_index && adj_rowptr && adj_src && adj_eid && shift_idx && counts &&
+                (vec || !dist));
+  triplet_count_pbc_kernel<<<triplet_grid_for(n_edges), 256, 0, as_stream(stream)>>>(
+      vec, edge_index, n_edges, adj_rowptr, adj_src, adj_eid, shift_idx, counts, dist);
+  return launch_status();
+}
+
+int gmp_triplet_fill_pbc_f32(const float* vec, const int64_t* edge_index, int64_t n_edges,
+                             int64_t n_nodes, const int64_t* adj_rowptr, const int64_t* adj_src,
+                             const int64_t* adj_eid, const int32_t* shift_idx,
+                             const int64_t* offsets, int64_t n_triplets, int64_t* idx_kj,
+                             int64_t* idx_ji, float* angle, void* stream) {
+  GMP_CHECK_ARG(n_edges >= 0 && n_nodes >= 0 && n_triplets >= 0);
+  if (n_triplets == 0) return GMP_OK;
+  GMP_CHECK_ARG(n_edges > 0 && edge_index && adj_rowptr && adj_src && adj_eid && shift_idx &&
+                offsets && idx_kj && idx_ji && (vec || !angle));
+  triplet_fill_pbc_kernel<<<(unsigned)ceil_div(n_edges, kFBp), kFBp, 0, as_stream(stream)>>>(
+      vec, edge_index, n_edges, adj_rowptr, adj_src, adj_eid, shift_idx, offsets, idx_kj,
+      idx_ji, angle);
+  return launch_status();
+}
+
+int gmp_triplet_vec_bwd_f32(const float* vec, int64_t n_edges, const int64_t* idx_kj,
+                            const int64_t* idx_ji, int64_t n_triplets, const float* grad_dist,
+                            const float* grad_angle, float* rows, void* stream) {
+  GMP_CHECK_ARG(n_edges >= 0 && n_triplets >= 0);
+  if (n_edges + n_triplets == 0) return GMP_OK;
+  GMP_CHECK_ARG(n_edges > 0 && vec && rows && (n_triplets == 0 || (idx_kj && idx_ji)));
+  triplet_vec_bwd_kernel<<<triplet_grid_for(n_edges + n_triplets), 256, 0,
+                           as_stream(stream)>>>(vec, n_edges, idx_kj, idx_ji, n_triplets,
+                                                grad_dist, grad_angle, rows);
+  return launch_status();
+}
+
+int gmp_triplet_vec_bwd2_f32(const float* vec, int64_t n_edges, const int64_t* idx_kj,
+                             const int64_t* idx_ji, int64_t n_triplets, const float* grad_dist,
+                             const float* grad_angle, const float* a_vec, float* gg_dist,
+                             float* gg_angle, float* rows, void* stream) {
+  GMP_CHECK_ARG(n_edges >= 0 && n_triplets >= 0);
+  if (n_edges + n_triplets == 0) return GMP_OK;
+  GMP_CHECK_ARG(n_edges > 0 && vec && a_vec && rows && (n_triplets == 0 || (idx_kj && idx_ji)));
+  triplet_vec_bwd2_kernel<<<triplet_grid_for(n_edges + n_triplets), 256, 0,
+                            as_stream(stream)>>>(vec, n_edges, idx_kj, idx_ji, n_triplets,
+                                                 grad_dist, grad_angle, a_vec, gg_dist,
+                                                 gg_angle, rows);
+  return launch_status();
+}
+
+}  // extern "C"

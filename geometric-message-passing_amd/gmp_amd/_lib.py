@@ -283,6 +283,12 @@ SIGNATURES = {
     "gmp_triplet_interact1_fwd_f32": (c_int, [c_i64, c_i64, c_i64, c_i64, c_int] + [c_vp] * 8),
     "gmp_triplet_interact1_bwd_partial_rows": (c_i64, [c_i64]),
     "gmp_triplet_interact1_bwd_f32": (c_int, [c_i64, c_i64, c_i64, c_int] + [c_vp] * 10),
+    # K11p: DimeNet's triplets on a periodic graph, edge-vector form; additions only
+    "gmp_triplet_count_pbc": (c_int, [c_vp, c_vp, c_i64, c_i64] + [c_vp] * 7),
+    "gmp_triplet_fill_pbc_f32": (c_int, [c_vp, c_vp, c_i64, c_i64] + [c_vp] * 5
+                                 + [c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "gmp_triplet_vec_bwd_f32": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64] + [c_vp] * 4),
+    "gmp_triplet_vec_bwd2_f32": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64] + [c_vp] * 7),
 }
 
 # include/gmp.h GMP_ABI_VERSION (6: r06 — K17 gmp_gvp_ff_{fwd,bwd}_f32, K15b gmp_egnn_node_bwd_f32;

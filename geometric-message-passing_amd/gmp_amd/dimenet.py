@@ -20,6 +20,7 @@ import torch
 from torch.nn import Embedding, Linear
 
 from . import ops
+from .graph import edge_shift
 from .spherenet import ResidualLayer, basis_tables, glorot_orthogonal, swish
 from .triplets import dimenet_angles, triplet_offsets
 
@@ -176,14 +177,22 @@ class DimeNetPPModel(torch.nn.Module):
     twice_differentiable (keyword-only; a plain attribute, not in the state_dict): inside
     gmp_amd.second_order() the model records twice-differentiable Functions (K11, K18d and K19d
     with their *_bwd2 kernels), so a loss on the forces -dE/dpos can be trained.  False, or
-    outside the context: the once-differentiable path, on which a second backward raises."""
+    outside the context: the once-differentiable path, on which a second backward raises.
+
+    periodic (keyword-only; a plain attribute as well): a batch that carries edge_shift_idx (and
+    cell) runs K11p, the image-aware triplets of include/gmp.h, with dist and angle from the
+    edge vectors (pos[j] - pos[i]) + graph.edge_shift(batch); forces, the stress
+    (energy_and_forces(stress=True)) and, with twice_differentiable, training on them work as for
+    an open structure.  Off (the default), such a batch raises NotImplementedError; a batch
+    without edge_shift_idx runs the open-boundary path either way."""
 
     def __init__(self, hidden_channels=128, in_dim=1, out_dim=1, num_layers=4, int_emb_size=64,
                  basis_emb_size=8, out_emb_channels=256, num_spherical=7, num_radial=6, cutoff=10,
                  max_num_neighbors=32, envelope_exponent=5, num_before_skip=1, num_after_skip=2,
-                 num_output_layers=3, act='swish', *, twice_differentiable=False):
+                 num_output_layers=3, act='swish', *, twice_differentiable=False, periodic=False):
         super().__init__()
         self.twice_differentiable = bool(twice_differentiable)
+        self.periodic = bool(periodic)
         if num_spherical < 2:
             raise ValueError("num_spherical should be greater than 1")
         act = _activation(act)
@@ -233,16 +242,26 @@ class DimeNetPPModel(torch.nn.Module):
         return ops.DimeTripletProjFn.apply(sbe, angle, idx_kj, self.sbf.pref, n, k, L, *weights)
 
     def forward(self, batch):
-        if getattr(batch, "edge_shift_idx", None) is not None:
-            raise NotImplementedError("DimeNetPPModel: periodic shifts (edge_shift_idx) are not "
-                                      "supported: K11's triplets take no periodic images")
+        shift_idx = getattr(batch, "edge_shift_idx", None)
+        shift = None
+        if shift_idx is not None:
+            if not getattr(self, "periodic", False):
+                raise NotImplementedError(
+                    "DimeNetPPModel: periodic shifts (edge_shift_idx) need a model built (or "
+                    "set) with periodic=True: K11's open-boundary triplets take no periodic "
+                    "images")
+            shift = edge_shift(batch)  # ValueError without batch.cell, before any device work
         z, pos, edge_index = batch.atoms, batch.pos, batch.edge_index
         ops._need_cuda(z, pos, edge_index, batch.batch)
         twice = self._twice()
-        if pos.requires_grad and torch.is_grad_enabled() and not twice:
-            pos = ops.FirstOrderOnlyFn.apply(pos)  # forces yes, training through them no
+        if torch.is_grad_enabled() and not twice:  # forces / stress yes, training through them no
+            if pos.requires_grad:
+                pos = ops.FirstOrderOnlyFn.apply(pos)
+            if shift is not None and shift.requires_grad:
+                shift = ops.FirstOrderOnlyFn.apply(shift)
         dist, angle, i, j, _, _, _, idx_kj, idx_ji = dimenet_angles(
-            pos, edge_index, z.size(0), twice_differentiable=twice)
+            pos, edge_index, z.size(0), twice_differentiable=twice, shift=shift,
+            shift_idx=shift_idx)
         return self.forward_from_geometry(z, dist, angle, i, j, idx_kj, idx_ji, batch.batch,
                                           num_graphs=getattr(batch, "num_graphs", None))
 

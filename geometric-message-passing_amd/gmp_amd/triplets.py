@@ -189,6 +189,160 @@ class TripletGeomBwdFn(torch.autograd.Function):
                 gg_a if g_angle is not None and need[5] else None, None, None)
 
 
+# --------------------------------------------------------------------------- periodic (K11p)
+def _run_pbc(vec, edge_index, num_nodes, shift_idx, want_angle=True, want_dist=True):
+    """K11p (include/gmp.h): the image-aware triplets of a periodic graph with dist / angle from
+    the per-edge vectors vec (E, 3); vec None: the lists only.  -> dist, angle, idx_kj, idx_ji."""
+    lib = _lib.load()
+    ei = ops._i64c(edge_index)
+    ops._need_cuda(ei, shift_idx)
+    E = ei.shape[1]
+    if tuple(shift_idx.shape) != (E, 3):
+        raise ValueError(f"shift_idx of shape {tuple(shift_idx.shape)}, expected ({E}, 3)")
+    sidx = shift_idx.to(torch.int32).contiguous()
+    if vec is not None:
+        vec = ops._f32c(vec.detach())
+        ops._need_cuda(vec)
+        if tuple(vec.shape) != (E, 3):
+            raise ValueError(f"vec of shape {tuple(vec.shape)}, expected ({E}, 3)")
+    else:
+        want_angle = want_dist = False
+    dev = ei.device
+    N = int(num_nodes)
+    if E == 0:  # nothing to launch
+        i64 = torch.empty(0, dtype=torch.int64, device=dev)
+        f32 = torch.empty(0, dtype=torch.float32, device=dev)
+        return (f32 if want_dist else None, f32.clone() if want_angle else None, i64,
+                i64.clone())
+    rowptr, asrc, aeid = adjacency_by_target(ei, N)
+    counts = torch.empty(E, dtype=torch.int64, device=dev)
+    dist = torch.empty(E, dtype=torch.float32, device=dev) if want_dist else None
+    s = ops._stream()
+    ops.check(lib.gmp_triplet_count_pbc(ops._p(vec), ops._p(ei), E, N, ops._p(rowptr),
+                                        ops._p(asrc), ops._p(aeid), ops._p(sidx), ops._p(counts),
+                                        ops._p(dist), s), "gmp_triplet_count_pbc")
+    offs = torch.zeros(E + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(counts, 0, out=offs[1:])
+    T = int(offs[-1].item())
+    idx_kj = torch.empty(T, dtype=torch.int64, device=dev)
+    idx_ji = torch.empty(T, dtype=torch.int64, device=dev)
+    angle = torch.empty(T, dtype=torch.float32, device=dev) if want_angle else None
+    ops.check(lib.gmp_triplet_fill_pbc_f32(ops._p(vec), ops._p(ei), E, N, ops._p(rowptr),
+                                           ops._p(asrc), ops._p(aeid), ops._p(sidx),
+                                           ops._p(offs), T, ops._p(idx_kj), ops._p(idx_ji),
+                                           ops._p(angle), s), "gmp_triplet_fill_pbc_f32")
+    return dist, angle, idx_kj, idx_ji
+
+
+def _rows_to_vec(rows, idx_kj, idx_ji, E, dtype):
+    """g_vec (E, 3) from the (2T + E, 3) rows of the vector-form kernels: the per-edge rows, plus
+    the rows of edge idx_ji[t] summed over the triplet offsets, plus the rows of edge idx_kj[t]
+    summed over the CSR of idx_kj (both cached per graph; deterministic)."""
+    T = idx_kj.numel()
+    g = rows[2 * T:]
+    if T:
+        own, _ = ops.segment_reduce(rows[:T], ops.get_csr(idx_ji, E), "sum", use_perm=False)
+        g = g + own + ops._sum_rows_per_edge(rows[T:2 * T], idx_kj, g)
+    return g.to(dtype)
+
+
+def _vec_bwd(vec, idx_kj, idx_ji, g_dist, g_angle):
+    E, T = vec.shape[0], idx_kj.numel()
+    rows = torch.empty((2 * T + E, 3), dtype=torch.float32, device=vec.device)
+    gd = ops._f32c(g_dist) if g_dist is not None else None
+    ga = ops._f32c(g_angle) if g_angle is not None else None
+    ops.check(_lib.load().gmp_triplet_vec_bwd_f32(
+        ops._p(ops._f32c(vec)), E, ops._p(idx_kj), ops._p(idx_ji), T, ops._p(gd), ops._p(ga),
+        ops._p(rows), ops._stream()), "gmp_triplet_vec_bwd_f32")
+    return _rows_to_vec(rows, idx_kj, idx_ji, E, vec.dtype)
+
+
+class TripletVecGeomFn(torch.autograd.Function):
+    """(dist (E), angle (T), idx_kj, idx_ji) of K11p from vec (E, 3) with the backward of dist and
+    angle w.r.t. vec (gmp_triplet_vec_bwd_f32); once differentiable."""
+
+    @staticmethod
+    def forward(ctx, vec, edge_index, num_nodes, shift_idx):
+        dist, angle, idx_kj, idx_ji = _run_pbc(vec, edge_index, num_nodes, shift_idx)
+        ctx.save_for_backward(vec, idx_kj, idx_ji)
+        ctx.mark_non_differentiable(idx_kj, idx_ji)
+        ctx.set_materialize_grads(False)
+        return dist, angle, idx_kj, idx_ji
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_dist, g_angle, _g1, _g2):
+        vec, idx_kj, idx_ji = ctx.saved_tensors
+        if not ctx.needs_input_grad[0] or (g_dist is None and g_angle is None):
+            return None, None, None, None
+        return _vec_bwd(vec, idx_kj, idx_ji, g_dist, g_angle), None, None, None
+
+
+class TripletVecGeom2Fn(torch.autograd.Function):
+    """TripletVecGeomFn whose backward is recorded (TripletVecGeomBwdFn), so that d vec can be
+    differentiated once more: energy-and-force training on a periodic structure."""
+
+    @staticmethod
+    def forward(ctx, vec, edge_index, num_nodes, shift_idx):
+        dist, angle, idx_kj, idx_ji = _run_pbc(vec, edge_index, num_nodes, shift_idx)
+        ctx.save_for_backward(vec, idx_kj, idx_ji)
+        ctx.mark_non_differentiable(idx_kj, idx_ji)
+        ctx.set_materialize_grads(False)
+        return dist, angle, idx_kj, idx_ji
+
+    @staticmethod
+    def backward(ctx, g_dist, g_angle, _g1, _g2):
+        vec, idx_kj, idx_ji = ctx.saved_tensors
+        if not ctx.needs_input_grad[0] or (g_dist is None and g_angle is None):
+            return None, None, None, None
+        return TripletVecGeomBwdFn.apply(vec, idx_kj, idx_ji, g_dist, g_angle), None, None, None
+
+
+class TripletVecGeomBwdFn(torch.autograd.Function):
+    """d vec (E, 3) from vec and the cotangents g_dist (E) / g_angle (T), each possibly None
+    (gmp_triplet_vec_bwd_f32 and the per-edge sums); backward by gmp_triplet_vec_bwd2_f32.  The
+    tensors given are saved as they are (a copy made here would be cut off from the graph).  The
+    second backward is once-differentiable."""
+
+    @staticmethod
+    def forward(ctx, vec, idx_kj, idx_ji, g_dist, g_angle):
+        ctx.save_for_backward(vec, idx_kj, idx_ji, g_dist, g_angle)
+        return _vec_bwd(vec, idx_kj, idx_ji, g_dist, g_angle)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, a_vec):
+        vec, idx_kj, idx_ji, g_dist, g_angle = ctx.saved_tensors
+        E, T = vec.shape[0], idx_kj.numel()
+        dev = vec.device
+        need = ctx.needs_input_grad
+        rows = torch.empty((2 * T + E, 3), dtype=torch.float32, device=dev)
+        gg_d = torch.empty(E, dtype=torch.float32, device=dev)
+        gg_a = torch.empty(T, dtype=torch.float32, device=dev)
+        gd = ops._f32c(g_dist) if g_dist is not None else None
+        ga = ops._f32c(g_angle) if g_angle is not None else None
+        ops.check(_lib.load().gmp_triplet_vec_bwd2_f32(
+            ops._p(ops._f32c(vec)), E, ops._p(idx_kj), ops._p(idx_ji), T, ops._p(gd), ops._p(ga),
+            ops._p(ops._f32c(a_vec)), ops._p(gg_d), ops._p(gg_a), ops._p(rows), ops._stream()),
+            "gmp_triplet_vec_bwd2_f32")
+        h_vec = _rows_to_vec(rows, idx_kj, idx_ji, E, vec.dtype) if need[0] else None
+        return (h_vec, None, None, gg_d if g_dist is not None and need[3] else None,
+                gg_a if g_angle is not None and need[4] else None)
+
+
+def edge_vectors(pos, edge_index, shift):
+    """vec (E, 3) = (pos[j] - pos[i]) + t, the K9p contract's featurised vector, in recorded ops
+    (EdgePosDiffFn and an add: differentiable in pos and shift to any order)."""
+    return ops.EdgePosDiffFn.apply(pos, ops._i64c(edge_index)) + shift
+
+
+def _geom_pbc(vec, edge_index, num_nodes, shift_idx, twice=False):
+    if vec.requires_grad and torch.is_grad_enabled():
+        fn = TripletVecGeom2Fn if twice else TripletVecGeomFn
+        return fn.apply(vec, edge_index, num_nodes, shift_idx)
+    return _run_pbc(vec, edge_index, num_nodes, shift_idx)
+
+
 def _geom(pos, edge_index, num_nodes, mode, use_torsion=False, twice=False):
     if pos.requires_grad and torch.is_grad_enabled():
         if twice:
@@ -210,20 +364,37 @@ def xyz_to_dat(pos, edge_index, num_nodes, use_torsion=False):
     return dist, angle, i, j, idx_kj, idx_ji
 
 
-def dimenet_triplets(edge_index, num_nodes):
+def dimenet_triplets(edge_index, num_nodes, shift_idx=None):
     """PyG DimeNet.triplets as called at dimenet.py:79:
-    -> col, row, idx_i, idx_j, idx_k, idx_kj, idx_ji."""
-    _, _, _, idx_kj, idx_ji = _run(None, edge_index, num_nodes, 1, False, False, False)
+    -> col, row, idx_i, idx_j, idx_k, idx_kj, idx_ji.  With shift_idx (E, 3) the image-aware
+    triplets of a periodic graph (K11p: only the reverse image of an edge is left out)."""
+    if shift_idx is not None:
+        _, _, idx_kj, idx_ji = _run_pbc(None, edge_index, num_nodes, shift_idx)
+    else:
+        _, _, _, idx_kj, idx_ji = _run(None, edge_index, num_nodes, 1, False, False, False)
     row, col = edge_index
     return col, row, col[idx_ji], row[idx_ji], row[idx_kj], idx_kj, idx_ji
 
 
-def dimenet_angles(pos, edge_index, num_nodes, twice_differentiable=False):
+def dimenet_angles(pos, edge_index, num_nodes, twice_differentiable=False, shift=None,
+                   shift_idx=None):
     """dimenet.py:79-90: -> dist (E), angle (T, vertex i), i, j, idx_i, idx_j, idx_k, idx_kj,
     idx_ji.  With twice_differentiable the backward to pos is recorded (TripletGeom2Fn), so a
-    force can be differentiated again."""
-    dist, angle, _, idx_kj, idx_ji = _geom(pos, edge_index, num_nodes, 1,
-                                           twice=twice_differentiable)
+    force can be differentiated again.
+
+    Periodic graphs (K11p, the contract of include/gmp.h): shift (E, 3), the Cartesian shift of
+    each edge's image (graph.edge_shift), and shift_idx (E, 3), its integer triple, are given
+    together.  The triplets are image-aware, dist and angle are functions of the edge vectors
+    (pos[j] - pos[i]) + shift and differentiable in pos and shift (so in the cell)."""
+    if (shift is None) != (shift_idx is None):
+        raise ValueError("dimenet_angles: shift and shift_idx are given together")
+    if shift_idx is not None:
+        vec = edge_vectors(pos, edge_index, shift)
+        dist, angle, idx_kj, idx_ji = _geom_pbc(vec, edge_index, num_nodes, shift_idx,
+                                                twice=twice_differentiable)
+    else:
+        dist, angle, _, idx_kj, idx_ji = _geom(pos, edge_index, num_nodes, 1,
+                                               twice=twice_differentiable)
     row, col = edge_index
     return (dist, angle, col, row, col[idx_ji], row[idx_ji], row[idx_kj], idx_kj, idx_ji)
 

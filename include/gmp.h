@@ -903,6 +903,56 @@ int gmp_triplet_torsion_bwd_f32(const float* pos, const int64_t* edge_index, int
                                 void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * K11p: DimeNet's triplets and angles on a periodic graph (gmp_triplet_pbc.hip).  The contract:
+ * an edge is e = (j -> i, S_e): source edge_index[0][e], target edge_index[1][e], image
+ * shift_idx[e] (an int32 triple).  Its vector is the K9p contract's featurised vector
+ *   vec_e = (pos[j] - pos[i]) + t_e,  t_e from gmp_edge_shift_vectors_f32
+ * (a subtraction, then an addition, each rounded in fp32); the caller forms vec (E, 3).
+ *   triplets of e: all entries kj = (k -> j, S_kj) of j's in-adjacency except those with k == i
+ *          AND S_kj == -S_e: the reverse image of e, an exact integer compare.  A self-image
+ *          edge (i == j, S != 0) follows the same rule; k == i with S_kj != -S_e is another
+ *          image of i and is kept; every entry that matches (a duplicated (j, i, S)) is excluded.
+ *   order: edges in edge order (idx_ji non-decreasing); within an edge the order of the
+ *          adjacency (ascending k, then ascending edge id; for a K9p graph ascending S).
+ *   dist[e] = len3(vec_e): with all shifts zero bit-equal to K11's dist.
+ *   angle[t] = atan2f(norm3(cross3(u, v)), dot3(u, v)), u = vec_ji, v = u + vec_kj (one rounded
+ *          add per component; v is the image of k relative to i), the helpers those of K11.
+ *          With zero shifts the triplet lists equal K11's (mode 1) and the angle differs from
+ *          its p_k - p_i form only by rounding.
+ * Mode 1 (DimeNet, vertex i) only; no torsion.  adj_* as for K11.
+ *   count: counts[e] = in-degree(j) - #excluded entries; dist (may be NULL; needs vec).
+ *   fill:  idx_kj / idx_ji (T) and angle (T; may be NULL; needs vec) for the offsets (E + 1)
+ *          that are the exclusive prefix sums of counts.
+ * ------------------------------------------------------------------------------------------ */
+int gmp_triplet_count_pbc(const float* vec, const int64_t* edge_index, int64_t n_edges,
+                          int64_t n_nodes, const int64_t* adj_rowptr, const int64_t* adj_src,
+                          const int64_t* adj_eid, const int32_t* shift_idx, int64_t* counts,
+                          float* dist, void* stream);
+int gmp_triplet_fill_pbc_f32(const float* vec, const int64_t* edge_index, int64_t n_edges,
+                             int64_t n_nodes, const int64_t* adj_rowptr, const int64_t* adj_src,
+                             const int64_t* adj_eid, const int32_t* shift_idx,
+                             const int64_t* offsets, int64_t n_triplets, int64_t* idx_kj,
+                             int64_t* idx_ji, float* angle, void* stream);
+/* Backward of dist (E) and angle (T) of K11p w.r.t. vec (E, 3), in edge-vector form (no node
+ * ids, no sort).  Writes rows (2T + E, 3): [0, T) g_u + g_v, the share of edge idx_ji[t];
+ * [T, 2T) g_v, the share of edge idx_kj[t]; [2T, 2T + E) grad_dist vec / d.  d vec = rows[2T:]
+ * + the sum of rows[:T] over the triplet offsets + the sum of rows[T:2T] over a CSR of idx_kj
+ * (deterministic, no atomics).  grad_dist / grad_angle may be NULL (zero). */
+int gmp_triplet_vec_bwd_f32(const float* vec, int64_t n_edges, const int64_t* idx_kj,
+                            const int64_t* idx_ji, int64_t n_triplets, const float* grad_dist,
+                            const float* grad_angle, float* rows, void* stream);
+/* Second backward of the same: a_vec (E, 3) is the cotangent of d vec, a_u = a_vec[ji] and
+ * a_v = a_vec[ji] + a_vec[kj].  Writes gg_dist (E) = a_vec . vec / d and gg_angle (T) =
+ * a_u.dtheta/du + a_v.dtheta/dv (either may be NULL) and rows (2T + E, 3) in the layout above:
+ * the directional derivative along a_vec of the rows gmp_triplet_vec_bwd_f32 writes.  u, v,
+ * a_u, a_v are formed in fp32, the rest in double, rounded once.  A collinear triplet (b = 0
+ * drops the c^ terms), a zero-length edge and a zero cotangent follow the first backward. */
+int gmp_triplet_vec_bwd2_f32(const float* vec, int64_t n_edges, const int64_t* idx_kj,
+                             const int64_t* idx_ji, int64_t n_triplets, const float* grad_dist,
+                             const float* grad_angle, const float* a_vec, float* gg_dist,
+                             float* gg_angle, float* rows, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * K12 fused LayerNorm + activation over rows (node-level MLPs: EGNN mlp_upd,
  * egnn_layer.py:37-39 / :82-86; GVP scalar LayerNorm, gvp_layer.py:221-243 with act = 2).
  * x (rows, d), d <= 512; act 0 relu, 1 silu, 2 identity.  Forward writes y = act(LN(x)) and
