@@ -203,12 +203,186 @@ __global__ void triplet_vec_bwd2_kernel(const float* __restrict__ vec, int64_t E
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// SphereNet's angle and torsion on the lists above (the K11p contract, "SphereNet" part): for
+// triplet t of edge e, u = 0 - vec_e, v = vec[idx_kj[t]], angle at j; the torsion is the minimum
+// over the triplets t' of the same edge (w = vec[idx_kj[t']]) of atan2(b, a) mapped to (0, 2 pi].
+// With zero shifts this is triplet_fill_kernel's mode 0 bit for bit, so the two places where
+// that kernel as compiled for gfx950 departs from its source's operation order are pinned here
+// (read from its assembly): the sums of dot3 stay uncontracted, and |u| of the torsion is
+// sqrt(fma(x, x, y y) + z z).  cross3 / norm3 are explicit fma chains and compile as written.
+constexpr float kTwoPi = 6.283185307179586f;
+
+__device__ __forceinline__ float dot3_k11(V3 a, V3 b) {
+#pragma clang fp contract(off)
+  const float xx = a.x * b.x, yy = a.y * b.y, zz = a.z * b.z;
+  return ((0.f + xx) + yy) + zz;
+}
+__device__ __forceinline__ float len3_tor_k11(V3 a) {
+#pragma clang fp contract(off)
+  const float yy = a.y * a.y, zz = a.z * a.z;
+  return __fsqrt_rn(__builtin_fmaf(a.x, a.x, yy) + zz);
+}
+
+// A thread per triplet; it walks the candidate range [offs[e], offs[e+1]) of its edge (K11's
+// form).  plane2 is recomputed per pair: 9 of the ~110 VALU operations of a pair, the rest is
+// the division and atan2f.
+__global__ void triplet_dat_pbc_kernel(const float* __restrict__ vec,
+                                       const int64_t* __restrict__ idx_kj,
+                                       const int64_t* __restrict__ idx_ji,
+                                       const int64_t* __restrict__ offs, int64_t T,
+                                       float* __restrict__ angle, float* __restrict__ torsion,
+                                       int64_t* __restrict__ torsion_arg) {
+#pragma clang fp contract(off)
+  const V3 zero{0.f, 0.f, 0.f};
+  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < T;
+       t += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t e = idx_ji[t];
+    const V3 u = sub3(zero, ld3(vec, e)), v = ld3(vec, idx_kj[t]);
+    const V3 plane1 = cross3(u, v);
+    if (angle) angle[t] = atan2f(norm3(plane1), dot3_k11(u, v));
+    if (!torsion) continue;
+    const float dji = len3_tor_k11(u);
+    float best = 3.402823466e38f;  // torch_scatter min: identity FLT_MAX, NaN never wins
+    int64_t arg = -1;                // first among equal minima
+    const int64_t o1 = offs[e + 1];
+    for (int64_t c = offs[e]; c < o1; ++c) {
+      const V3 w = ld3(vec, idx_kj[c]);
+      const V3 plane2 = cross3(u, w);
+      const float a = dot3_k11(plane1, plane2);
+      const float b = dot3_k11(cross3(plane1, plane2), u) / dji;
+      float t1 = atan2f(b, a);
+      if (t1 <= 0.f) t1 = t1 + kTwoPi;
+      if (t1 < best) {
+        best = t1;
+        arg = c;
+      }
+    }
+    torsion[t] = best == 3.402823466e38f ? 0.f : best;
+    torsion_arg[t] = arg;
+  }
+}
+
+__device__ __forceinline__ V3 xf3(V3 a, V3 b) {
+  return V3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
+}
+__device__ __forceinline__ V3 acc3(V3 a, V3 b) { return V3{a.x + b.x, a.y + b.y, a.z + b.z}; }
+
+// Reverse mode of one candidate's t1 = atan2(b, a) scaled by g (the derivation is the comment
+// above triplet_torsion_bwd_kernel in gmp_triplet.hip; the 2 pi shift has unit derivative).
+// Dead cases, zero outputs: g == 0, a^2 + b^2 == 0 (an exactly collinear triplet, a candidate
+// exactly parallel to u) and |u| == 0.
+__device__ __forceinline__ void torsion_bwd(V3 u, V3 v, V3 w, float g, V3& gu, V3& gv, V3& gw) {
+  const V3 z{0.f, 0.f, 0.f};
+  gu = z; gv = z; gw = z;
+  if (g == 0.f) return;
+  const V3 P = cross3(u, v), Q = cross3(u, w), R = cross3(P, Q);
+  const float a = dot3(P, Q), c = dot3(R, u), L = len3(u);
+  if (!(L > 0.f)) return;
+  const float b = c / L;
+  const float den = a * a + b * b;
+  if (!(den > 0.f)) return;
+  const float ga = -g * b / den, gb = g * a / den;
+  const float gc = gb / L, gL = -gb * c / (L * L);
+  gu = V3{gL * u.x / L + gc * R.x, gL * u.y / L + gc * R.y, gL * u.z / L + gc * R.z};
+  const V3 gR{gc * u.x, gc * u.y, gc * u.z};
+  V3 gP = xf3(Q, gR), gQ = xf3(gR, P);
+  gP = V3{gP.x + ga * Q.x, gP.y + ga * Q.y, gP.z + ga * Q.z};
+  gQ = V3{gQ.x + ga * P.x, gQ.y + ga * P.y, gQ.z + ga * P.z};
+  gu = acc3(gu, acc3(xf3(v, gP), xf3(w, gQ)));
+  gv = xf3(gP, u);
+  gw = xf3(gQ, u);
+}
+
+// First backward of dist, angle and torsion in edge-vector form.  rows (2T + E, 3) in the layout
+// of triplet_vec_bwd_kernel: [0, T) -g_u, the share of edge idx_ji[t] (u = -vec_e); [T, 2T) the
+// share of edge idx_kj[t]: g_v of the triplet's own angle and torsion, plus g_w of every triplet
+// of the same edge whose winner is t (gathered by walking the edge's range in index order:
+// integer compares, a fixed order, no atomics); [2T, 2T + E) g_dist vec / d.  A winner outside
+// the edge's range (-1: none) gives the torsion no rows.
+__global__ void triplet_dat_vec_bwd_kernel(const float* __restrict__ vec, int64_t E,
+                                           const int64_t* __restrict__ idx_kj,
+                                           const int64_t* __restrict__ idx_ji,
+                                           const int64_t* __restrict__ offs,
+                                           const int64_t* __restrict__ targ, int64_t T,
+                                           const float* __restrict__ g_dist,
+                                           const float* __restrict__ g_angle,
+                                           const float* __restrict__ g_tor,
+                                           float* __restrict__ rows) {
+  const int64_t n = T + E;
+  const V3 zero{0.f, 0.f, 0.f};
+  for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < n;
+       q += (int64_t)gridDim.x * blockDim.x) {
+    if (q < T) {
+      const int64_t t = q, e = idx_ji[t];
+      const V3 u = sub3(zero, ld3(vec, e)), v = ld3(vec, idx_kj[t]);
+      V3 gu, gv;
+      angle_bwd(u, v, g_angle ? g_angle[t] : 0.f, gu, gv);
+      if (g_tor) {
+        const int64_t o0 = offs[e], o1 = offs[e + 1], arg = targ[t];
+        V3 tu, tv, tw;
+        if (arg >= o0 && arg < o1) {
+          torsion_bwd(u, v, ld3(vec, idx_kj[arg]), g_tor[t], tu, tv, tw);
+          gu = acc3(gu, tu);
+          gv = acc3(gv, tv);
+        }
+        for (int64_t c = o0; c < o1; ++c) {
+          if (targ[c] != t) continue;
+          torsion_bwd(u, ld3(vec, idx_kj[c]), v, g_tor[c], tu, tv, tw);
+          gv = acc3(gv, tw);
+        }
+      }
+      float* r0 = rows + 3 * t;
+      float* r1 = rows + 3 * (T + t);
+      r0[0] = -gu.x; r0[1] = -gu.y; r0[2] = -gu.z;
+      r1[0] = gv.x; r1[1] = gv.y; r1[2] = gv.z;
+    } else {
+      const int64_t e = q - T;
+      const V3 d = ld3(vec, e);
+      const float len = len3(d);
+      const float g = g_dist ? g_dist[e] : 0.f;
+      const float s = (g != 0.f && len > 0.f) ? g / len : 0.f;
+      float* r = rows + 3 * (2 * T + e);
+      r[0] = s * d.x; r[1] = s * d.y; r[2] = s * d.z;
+    }
+  }
+}
+
 }  // namespace
 }  // namespace gmp
 
 using namespace gmp;
 
 extern "C" {
+
+int gmp_triplet_dat_pbc_f32(const float* vec, int64_t n_edges, const int64_t* idx_kj,
+                            const int64_t* idx_ji, const int64_t* offsets, int64_t n_triplets,
+                            float* angle, float* torsion, int64_t* torsion_arg, void* stream) {
+  GMP_CHECK_ARG(n_edges >= 0 && n_triplets >= 0);
+  GMP_CHECK_ARG((torsion == nullptr) == (torsion_arg == nullptr));
+  if (n_triplets == 0) return GMP_OK;
+  GMP_CHECK_ARG(n_edges > 0 && vec && idx_kj && idx_ji && (angle || torsion) &&
+                (offsets || !torsion));
+  triplet_dat_pbc_kernel<<<triplet_grid_for(n_triplets), 256, 0, as_stream(stream)>>>(
+      vec, idx_kj, idx_ji, offsets, n_triplets, angle, torsion, torsion_arg);
+  return launch_status();
+}
+
+int gmp_triplet_dat_vec_bwd_f32(const float* vec, int64_t n_edges, const int64_t* idx_kj,
+                                const int64_t* idx_ji, const int64_t* offsets,
+                                const int64_t* torsion_arg, int64_t n_triplets,
+                                const float* grad_dist, const float* grad_angle,
+                                const float* grad_torsion, float* rows, void* stream) {
+  GMP_CHECK_ARG(n_edges >= 0 && n_triplets >= 0);
+  if (n_edges + n_triplets == 0) return GMP_OK;
+  GMP_CHECK_ARG(n_edges > 0 && vec && rows && (n_triplets == 0 || (idx_kj && idx_ji)));
+  GMP_CHECK_ARG(n_triplets == 0 || !grad_torsion || (offsets && torsion_arg));
+  triplet_dat_vec_bwd_kernel<<<triplet_grid_for(n_edges + n_triplets), 256, 0,
+                               as_stream(stream)>>>(vec, n_edges, idx_kj, idx_ji, offsets,
+                                                    torsion_arg, n_triplets, grad_dist,
+                                                    grad_angle, grad_torsion, rows);
+  return launch_status();
+}
 
 int gmp_triplet_count_pbc(const float* vec, const int64_t* edge_index, int64_t n_edges,
                           int64_t n_nodes, const int64_t* adj_rowptr, const int64_t* adj_src,

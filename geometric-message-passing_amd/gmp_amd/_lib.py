@@ -289,6 +289,10 @@ SIGNATURES = {
                                  + [c_i64, c_vp, c_vp, c_vp, c_vp]),
     "gmp_triplet_vec_bwd_f32": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64] + [c_vp] * 4),
     "gmp_triplet_vec_bwd2_f32": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64] + [c_vp] * 7),
+    # K11p: SphereNet's angle and torsion on the periodic lists, first backward; additions only
+    "gmp_triplet_dat_pbc_f32": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64] + [c_vp] * 4),
+    "gmp_triplet_dat_vec_bwd_f32": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64]
+                                    + [c_vp] * 5),
 }
 
 # include/gmp.h GMP_ABI_VERSION (6: r06 — K17 gmp_gvp_ff_{fwd,bwd}_f32, K15b gmp_egnn_node_bwd_f32;

@@ -41,9 +41,10 @@ def energy_and_forces(model, batch, create_graph=None, stress=False):
     stress=True (the batch carries a cell) returns (energy, forces, sigma) with sigma (B, 3, 3)
     = (1 / V) dE / d eps at eps = 0 under the symmetric strain pos -> pos + pos @ sym(eps)[batch],
     cell -> cell + cell @ sym(eps), applied to a shallow copy of the batch; V = |det cell|.
-    Periodic batches (edge_shift_idx, cell) run through SchNet, MACE, TFN and a DimeNetPPModel
-    built (or set) with periodic=True; with twice_differentiable=True as well, forces and sigma
-    of DimeNet++ can be trained on."""
+    Periodic batches (edge_shift_idx, cell) run through SchNet, MACE, TFN and a DimeNetPPModel or
+    SphereNetModel built (or set) with periodic=True; with twice_differentiable=True as well,
+    forces and sigma of DimeNet++ can be trained on (SphereNet: first order only, inference
+    forces and stress, and training on the energy)."""
     if create_graph is None:
         create_graph = torch.is_grad_enabled() and model.training
     pos = batch.pos

@@ -26,6 +26,7 @@ from torch import nn
 from torch.nn import Embedding, Linear
 
 from . import ops
+from .graph import edge_shift
 from .triplets import xyz_to_dat, triplet_offsets
 
 
@@ -320,16 +321,27 @@ class update_u(torch.nn.Module):
 
 # ----------------------------------------------------------------------------------- model
 class SphereNetModel(torch.nn.Module):
-    """SphereNet, "Spherical Message Passing for 3D Molecular Graphs" (models/spherenet.py)."""
+    """SphereNet, "Spherical Message Passing for 3D Molecular Graphs" (models/spherenet.py).
+
+    periodic (keyword-only; a plain attribute, present only when set): a batch that carries
+    edge_shift_idx (and cell) runs K11p, the image-aware triplets of include/gmp.h, with dist,
+    angle and torsion from the edge vectors (pos[j] - pos[i]) + graph.edge_shift(batch); forces
+    and the stress (energy_and_forces(stress=True)) and training on the energy work as for an
+    open structure (first order only).  Off (the default), such a batch raises
+    NotImplementedError; a batch without edge_shift_idx runs the open-boundary path either
+    way."""
 
     def __init__(self, cutoff=10, num_layers=4, hidden_channels=128, in_dim=1, out_dim=1,
                  int_emb_size=64, basis_emb_size_dist=8, basis_emb_size_angle=8,
                  basis_emb_size_torsion=8, out_emb_channels=128, num_spherical=7, num_radial=6,
                  envelope_exponent=5, num_before_skip=1, num_after_skip=2, num_output_layers=2,
-                 act=swish, output_init='GlorotOrthogonal', use_node_features=True):
+                 act=swish, output_init='GlorotOrthogonal', use_node_features=True, *,
+                 periodic=False):
         super().__init__()
         if num_layers < 1:
             raise ValueError("SphereNetModel needs at least one layer")
+        if periodic:  # a plain attribute, set only when asked for (forward reads it by getattr)
+            self.periodic = True
         self.cutoff = cutoff
         self.num_spherical, self.num_radial = num_spherical, num_radial
         self.init_e = init(num_radial, hidden_channels, act, use_node_features=use_node_features)
@@ -357,16 +369,25 @@ class SphereNetModel(torch.nn.Module):
             uv.reset_parameters()
 
     def forward(self, batch_data):
-        if getattr(batch_data, "edge_shift_idx", None) is not None:
-            raise NotImplementedError("SphereNetModel: periodic shifts (edge_shift_idx) are not "
-                                      "supported: K11's triplets take no periodic images")
+        shift_idx = getattr(batch_data, "edge_shift_idx", None)
+        shift = None
+        if shift_idx is not None:
+            if not getattr(self, "periodic", False):
+                raise NotImplementedError(
+                    "SphereNetModel: periodic shifts (edge_shift_idx) need a model built (or "
+                    "set) with periodic=True: K11's open-boundary triplets take no periodic "
+                    "images")
+            shift = edge_shift(batch_data)  # ValueError without batch.cell, before device work
         z, pos, batch = batch_data.atoms, batch_data.pos, batch_data.batch
         edge_index = batch_data.edge_index
         ops._need_cuda(z, pos, edge_index, batch)
-        if pos.requires_grad and torch.is_grad_enabled():
-            pos = ops.FirstOrderOnlyFn.apply(pos)  # forces yes, training through them no
-        dist, angle, torsion, i, j, idx_kj, idx_ji = xyz_to_dat(pos, edge_index, z.size(0),
-                                                                use_torsion=True)
+        if torch.is_grad_enabled():  # forces / stress yes, training through them no
+            if pos.requires_grad:
+                pos = ops.FirstOrderOnlyFn.apply(pos)
+            if shift is not None and shift.requires_grad:
+                shift = ops.FirstOrderOnlyFn.apply(shift)
+        dist, angle, torsion, i, j, idx_kj, idx_ji = xyz_to_dat(
+            pos, edge_index, z.size(0), use_torsion=True, shift=shift, shift_idx=shift_idx)
         return self.forward_from_geometry(z, dist, angle, torsion, i, j, idx_kj, idx_ji, batch,
                                           num_graphs=getattr(batch_data, "num_graphs", None))
 

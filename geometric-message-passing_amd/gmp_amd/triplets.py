@@ -15,6 +15,11 @@ gradient row per (triplet, corner) and per (edge, end), summed per node over a C
 spherenet_layer.py:535-559) is differentiable too: the fill kernel records the winning k_n of
 every triplet and gmp_triplet_torsion_bwd_f32 routes the gradient to that candidate only, as
 torch_scatter's scatter_min backward does (first index among equal minima).
+
+Periodic graphs (K11p, the contract of include/gmp.h) run in edge-vector form: the image-aware
+lists from shift_idx, dist / angle (and, for SphereNet, the torsion over the triplets of the same
+edge) from vec = (pos[j] - pos[i]) + shift, and backward kernels that return per-edge gradients
+summed over cached CSRs; pos and the cell are reached through the recorded linear maps.
 """
 import torch
 
@@ -190,9 +195,11 @@ class TripletGeomBwdFn(torch.autograd.Function):
 
 
 # --------------------------------------------------------------------------- periodic (K11p)
-def _run_pbc(vec, edge_index, num_nodes, shift_idx, want_angle=True, want_dist=True):
+def _run_pbc(vec, edge_index, num_nodes, shift_idx, want_angle=True, want_dist=True,
+             want_offsets=False):
     """K11p (include/gmp.h): the image-aware triplets of a periodic graph with dist / angle from
-    the per-edge vectors vec (E, 3); vec None: the lists only.  -> dist, angle, idx_kj, idx_ji."""
+    the per-edge vectors vec (E, 3); vec None: the lists only.  -> dist, angle, idx_kj, idx_ji
+    (and, with want_offsets, the triplet offsets (E + 1))."""
     lib = _lib.load()
     ei = ops._i64c(edge_index)
     ops._need_cuda(ei, shift_idx)
@@ -212,8 +219,8 @@ def _run_pbc(vec, edge_index, num_nodes, shift_idx, want_angle=True, want_dist=T
     if E == 0:  # nothing to launch
         i64 = torch.empty(0, dtype=torch.int64, device=dev)
         f32 = torch.empty(0, dtype=torch.float32, device=dev)
-        return (f32 if want_dist else None, f32.clone() if want_angle else None, i64,
-                i64.clone())
+        out = (f32 if want_dist else None, f32.clone() if want_angle else None, i64, i64.clone())
+        return out + (torch.zeros(1, dtype=torch.int64, device=dev),) if want_offsets else out
     rowptr, asrc, aeid = adjacency_by_target(ei, N)
     counts = torch.empty(E, dtype=torch.int64, device=dev)
     dist = torch.empty(E, dtype=torch.float32, device=dev) if want_dist else None
@@ -231,6 +238,8 @@ def _run_pbc(vec, edge_index, num_nodes, shift_idx, want_angle=True, want_dist=T
                                            ops._p(asrc), ops._p(aeid), ops._p(sidx),
                                            ops._p(offs), T, ops._p(idx_kj), ops._p(idx_ji),
                                            ops._p(angle), s), "gmp_triplet_fill_pbc_f32")
+    if want_offsets:
+        return dist, angle, idx_kj, idx_ji, offs
     return dist, angle, idx_kj, idx_ji
 
 
@@ -330,6 +339,71 @@ class TripletVecGeomBwdFn(torch.autograd.Function):
                 gg_a if g_angle is not None and need[4] else None)
 
 
+def _run_dat_pbc(vec, edge_index, num_nodes, shift_idx, use_torsion):
+    """SphereNet's geometry on a periodic graph (K11p, include/gmp.h): K11p's count and fill for
+    the lists and dist (angle = NULL), then gmp_triplet_dat_pbc_f32 for the angle at j and the
+    torsion with its winner.  -> dist, angle, torsion, idx_kj, idx_ji, offsets, torsion_arg
+    (torsion / torsion_arg None without use_torsion)."""
+    dist, _, idx_kj, idx_ji, offs = _run_pbc(vec, edge_index, num_nodes, shift_idx,
+                                             want_angle=False, want_offsets=True)
+    E, T = dist.numel(), idx_kj.numel()
+    dev = dist.device
+    angle = torch.empty(T, dtype=torch.float32, device=dev)
+    torsion = torch.empty(T, dtype=torch.float32, device=dev) if use_torsion else None
+    arg = torch.empty(T, dtype=torch.int64, device=dev) if use_torsion else None
+    v32 = ops._f32c(vec.detach())
+    ops.check(_lib.load().gmp_triplet_dat_pbc_f32(
+        ops._p(v32), E, ops._p(idx_kj), ops._p(idx_ji), ops._p(offs), T, ops._p(angle),
+        ops._p(torsion), ops._p(arg), ops._stream()), "gmp_triplet_dat_pbc_f32")
+    return dist, angle, torsion, idx_kj, idx_ji, offs, arg
+
+
+class TripletVecDatFn(torch.autograd.Function):
+    """(dist (E), angle (T, vertex j), torsion (T, or empty without use_torsion), idx_kj, idx_ji)
+    of SphereNet on a periodic graph from vec (E, 3), with the backward of dist, angle and torsion
+    w.r.t. vec (gmp_triplet_dat_vec_bwd_f32, the scatter-min's winner held fixed); once
+    differentiable."""
+
+    @staticmethod
+    def forward(ctx, vec, edge_index, num_nodes, shift_idx, use_torsion):
+        dist, angle, torsion, idx_kj, idx_ji, offs, arg = _run_dat_pbc(
+            vec, edge_index, num_nodes, shift_idx, use_torsion)
+        if torsion is None:
+            torsion = torch.empty(0, dtype=torch.float32, device=dist.device)
+            arg = torch.empty(0, dtype=torch.int64, device=dist.device)
+        ctx.save_for_backward(vec, idx_kj, idx_ji, offs, arg)
+        ctx.use_torsion = use_torsion
+        ctx.mark_non_differentiable(idx_kj, idx_ji)
+        ctx.set_materialize_grads(False)
+        return dist, angle, torsion, idx_kj, idx_ji
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_dist, g_angle, g_torsion, _g1, _g2):
+        vec, idx_kj, idx_ji, offs, arg = ctx.saved_tensors
+        if not ctx.use_torsion:
+            g_torsion = None
+        if not ctx.needs_input_grad[0] or (g_dist is None and g_angle is None
+                                           and g_torsion is None):
+            return None, None, None, None, None
+        E, T = vec.shape[0], idx_kj.numel()
+        rows = torch.empty((2 * T + E, 3), dtype=torch.float32, device=vec.device)
+        gd = ops._f32c(g_dist) if g_dist is not None else None
+        ga = ops._f32c(g_angle) if g_angle is not None else None
+        gt = ops._f32c(g_torsion) if g_torsion is not None else None
+        ops.check(_lib.load().gmp_triplet_dat_vec_bwd_f32(
+            ops._p(ops._f32c(vec)), E, ops._p(idx_kj), ops._p(idx_ji), ops._p(offs), ops._p(arg),
+            T, ops._p(gd), ops._p(ga), ops._p(gt), ops._p(rows), ops._stream()),
+            "gmp_triplet_dat_vec_bwd_f32")
+        return _rows_to_vec(rows, idx_kj, idx_ji, E, vec.dtype), None, None, None, None
+
+
+def _dat_pbc(vec, edge_index, num_nodes, shift_idx, use_torsion):
+    if vec.requires_grad and torch.is_grad_enabled():
+        return TripletVecDatFn.apply(vec, edge_index, num_nodes, shift_idx, use_torsion)
+    return _run_dat_pbc(vec, edge_index, num_nodes, shift_idx, use_torsion)[:5]
+
+
 def edge_vectors(pos, edge_index, shift):
     """vec (E, 3) = (pos[j] - pos[i]) + t, the K9p contract's featurised vector, in recorded ops
     (EdgePosDiffFn and an add: differentiable in pos and shift to any order)."""
@@ -353,11 +427,24 @@ def _geom(pos, edge_index, num_nodes, mode, use_torsion=False, twice=False):
     return _run(pos, edge_index, num_nodes, mode, True, use_torsion, True)
 
 
-def xyz_to_dat(pos, edge_index, num_nodes, use_torsion=False):
+def xyz_to_dat(pos, edge_index, num_nodes, use_torsion=False, *, shift=None, shift_idx=None):
     """spherenet_layer.py:496: -> dist, angle, [torsion,] i, j, idx_kj, idx_ji (edge e = j -> i;
     angle in [0, pi] at j; torsion in (0, 2*pi]).  dist, angle and torsion are differentiable
-    w.r.t. pos."""
-    dist, angle, torsion, idx_kj, idx_ji = _geom(pos, edge_index, num_nodes, 0, use_torsion)
+    w.r.t. pos.
+
+    Periodic graphs (K11p, the contract of include/gmp.h): shift (E, 3), the Cartesian shift of
+    each edge's image (graph.edge_shift), and shift_idx (E, 3), its integer triple, are given
+    together.  The triplets are image-aware, the torsion's candidates are the triplets of the
+    same edge, and dist, angle and torsion are functions of the edge vectors
+    (pos[j] - pos[i]) + shift, once differentiable in pos and shift (so in the cell)."""
+    if (shift is None) != (shift_idx is None):
+        raise ValueError("xyz_to_dat: shift and shift_idx are given together")
+    if shift_idx is not None:
+        vec = edge_vectors(pos, edge_index, shift)
+        dist, angle, torsion, idx_kj, idx_ji = _dat_pbc(vec, edge_index, num_nodes, shift_idx,
+                                                        use_torsion)
+    else:
+        dist, angle, torsion, idx_kj, idx_ji = _geom(pos, edge_index, num_nodes, 0, use_torsion)
     j, i = edge_index
     if use_torsion:
         return dist, angle, torsion, i, j, idx_kj, idx_ji
@@ -399,11 +486,12 @@ def dimenet_angles(pos, edge_index, num_nodes, twice_differentiable=False, shift
     return (dist, angle, col, row, col[idx_ji], row[idx_ji], row[idx_kj], idx_kj, idx_ji)
 
 
-def xyz_to_dat_offsets(pos, edge_index, num_nodes):
+def xyz_to_dat_offsets(pos, edge_index, num_nodes, *, shift=None, shift_idx=None):
     """xyz_to_dat(..., use_torsion=True) plus the triplet row pointer: -> dist, angle, torsion,
     i, j, idx_kj, idx_ji, offsets (E + 1), the triplets of edge e being the contiguous range
-    [offsets[e], offsets[e+1]) (idx_ji is non-decreasing)."""
-    dist, angle, torsion, i, j, idx_kj, idx_ji = xyz_to_dat(pos, edge_index, num_nodes, True)
+    [offsets[e], offsets[e+1]) (idx_ji is non-decreasing).  shift / shift_idx as xyz_to_dat."""
+    dist, angle, torsion, i, j, idx_kj, idx_ji = xyz_to_dat(pos, edge_index, num_nodes, True,
+                                                            shift=shift, shift_idx=shift_idx)
     return dist, angle, torsion, i, j, idx_kj, idx_ji, triplet_offsets(idx_ji, dist.numel())
 
 

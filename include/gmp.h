@@ -923,6 +923,26 @@ int gmp_triplet_torsion_bwd_f32(const float* pos, const int64_t* edge_index, int
  *   count: counts[e] = in-degree(j) - #excluded entries; dist (may be NULL; needs vec).
  *   fill:  idx_kj / idx_ji (T) and angle (T; may be NULL; needs vec) for the offsets (E + 1)
  *          that are the exclusive prefix sums of counts.
+ * SphereNet (mode 0: angle at vertex j, and the torsion) on the same lists: idx_kj, idx_ji, dist
+ * and the offsets are those of count / fill (angle = NULL), unchanged; gmp_triplet_dat_pbc_f32
+ * adds, for triplet t of edge e, with the helpers of K11 and operation by operation as its
+ * mode 0:
+ *   vectors: u = sub3(0, vec_e) (a subtraction from +0, not a sign flip: an equal coordinate
+ *          gives +0, as K11's p_i - p_j does), v = vec[idx_kj[t]].
+ *   angle[t] = atan2f(norm3(cross3(u, v)), dot3(u, v)), at vertex j, in [0, pi].
+ *   candidates of t: all triplets t' of the same edge, [offsets[e], offsets[e+1]), in index
+ *          order, t' = t included (the same kept adjacency entries; in the open case the
+ *          reference's "k_n != i", which keeps k_n = k); w = vec[idx_kj[t']].
+ *   t1(t, t'): plane1 = cross3(u, v), plane2 = cross3(u, w), a = dot3(plane1, plane2),
+ *          b = dot3(cross3(plane1, plane2), u) / len3(u) (a rounded division),
+ *          t1 = atan2f(b, a), and t1 + 2 pi (a rounded addition) if t1 <= 0.
+ *   torsion[t] = the minimum of t1 over the candidates by K11's rule: identity FLT_MAX, NaN
+ *          never wins, 0 if nothing won.  torsion_arg[t] = the TRIPLET index t' of the first
+ *          candidate among equal minima, -1 if none: the winning edge is
+ *          idx_kj[torsion_arg[t]], and a duplicated (j, i, S) resolves to the lower index.
+ * With all shifts zero this is K11's mode 0 bit for bit; for that, the sums of dot3 are kept
+ * uncontracted and len3(u) of the torsion is evaluated as sqrt(fma(x, x, y y) + z z), which is
+ * what K11's fill kernel does as compiled for gfx950 (pinned under fp contract(off)).
  * ------------------------------------------------------------------------------------------ */
 int gmp_triplet_count_pbc(const float* vec, const int64_t* edge_index, int64_t n_edges,
                           int64_t n_nodes, const int64_t* adj_rowptr, const int64_t* adj_src,
@@ -951,6 +971,28 @@ int gmp_triplet_vec_bwd2_f32(const float* vec, int64_t n_edges, const int64_t* i
                              const int64_t* idx_ji, int64_t n_triplets, const float* grad_dist,
                              const float* grad_angle, const float* a_vec, float* gg_dist,
                              float* gg_angle, float* rows, void* stream);
+/* SphereNet's angle (T) and torsion (T) with its winner torsion_arg (T) on the K11p lists (the
+ * contract above).  torsion and torsion_arg may be NULL together: angle only (offsets may then
+ * be NULL).  GMP_OK without a launch for n_triplets == 0. */
+int gmp_triplet_dat_pbc_f32(const float* vec, int64_t n_edges, const int64_t* idx_kj,
+                            const int64_t* idx_ji, const int64_t* offsets, int64_t n_triplets,
+                            float* angle, float* torsion, int64_t* torsion_arg, void* stream);
+/* First backward of dist (E), the mode-0 angle (T) and the torsion (T) w.r.t. vec (E, 3), in
+ * edge-vector form.  Writes rows (2T + E, 3) in the layout of gmp_triplet_vec_bwd_f32, summed the
+ * same way: [0, T) -g_u of angle and torsion, the share of edge idx_ji[t]; [T, 2T) the share of
+ * edge idx_kj[t]: g_v of the triplet's angle and torsion plus g_w of every triplet of the same
+ * edge whose winner torsion_arg is t (gathered in index order inside the kernel: no sort, no
+ * atomics, a fixed order); [2T, 2T + E) grad_dist vec / d (written for n_triplets == 0 too).
+ * The winner is held fixed (torch_scatter's arg routing); the 2 pi shift has unit derivative.
+ * Zero rows for a zero cotangent and, for the torsion, where a^2 + b^2 == 0 or len3(u) == 0 (an
+ * exactly collinear triplet, a candidate exactly parallel to u), where autograd gives NaN; the
+ * angle's dead cases are those of gmp_triplet_vec_bwd_f32.  Any of the three cotangents may be
+ * NULL (zero); offsets and torsion_arg are needed with grad_torsion only. */
+int gmp_triplet_dat_vec_bwd_f32(const float* vec, int64_t n_edges, const int64_t* idx_kj,
+                                const int64_t* idx_ji, const int64_t* offsets,
+                                const int64_t* torsion_arg, int64_t n_triplets,
+                                const float* grad_dist, const float* grad_angle,
+                                const float* grad_torsion, float* rows, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * K12 fused LayerNorm + activation over rows (node-level MLPs: EGNN mlp_upd,
