@@ -200,13 +200,46 @@ __global__ __launch_bounds__(kSC) void sc_bwd_coef_kernel(int64_t B, int C, int 
   }
 }
 
-unsigned node_blocks(int64_t B, int C, int CT) {
+// The launch decomposition of the three kernels for one shape: host arithmetic, shared by the
+// launches below and by gmp_sc_route.
+struct Route {
+  int CT, npb, ctiles;       // forward / dx: channels per tile, nodes per pass, channel tiles
+  unsigned nblocks;          // forward / dx: node blocks (grid-stride over nodes)
+  size_t lds_fwd, lds_dx;    // forward / dx: dynamic LDS bytes
+  int CTd, tpb, zblocks, NB; // dcoef: channels per tile, terms per workgroup, z-blocks, stage
+  int G;                     // dcoef: node groups
+  int64_t per;               // dcoef: nodes per group
+  size_t lds_coef;           // dcoef: dynamic LDS bytes
+};
+
+Route route_of(int64_t B, int C, int D, int M, int T) {
+  Route r;
+  r.CT = C < kMaxCT ? C : kMaxCT;
+  r.npb = kSC / r.CT;
+  r.ctiles = (int)ceil_div(C, r.CT);
   // enough workgroups for the chip (~8 per CU over the channel tiles), each sweeping nodes
-  const int64_t tiles = ceil_div((int64_t)C, (int64_t)CT);
-  int64_t want = ceil_div((int64_t)8 * device_cu_count(), tiles);
+  int64_t want = ceil_div((int64_t)8 * device_cu_count(), (int64_t)r.ctiles);
   if (want < 1) want = 1;
-  const int64_t most = ceil_div(B, (int64_t)(kSC / CT));
-  return (unsigned)(want < most ? want : most);
+  const int64_t most = ceil_div(B, (int64_t)r.npb);
+  r.nblocks = (unsigned)(want < most ? want : most);
+  r.lds_fwd = (size_t)kSC * row_stride(D) * sizeof(float);
+  r.lds_dx = 2 * r.lds_fwd;
+  r.G = gmp_sc_groups(B);
+  r.per = ceil_div(B, (int64_t)r.G);
+  // channels per tile: all of a tile's (term, channel) pairs in one workgroup (T = 0: no launch)
+  int CT = T > 0 ? kPairs / T : kMaxCT;
+  if (CT > kMaxCT) CT = kMaxCT;
+  if (CT > C) CT = C;
+  if (CT < 1) CT = 1;
+  r.CTd = CT;
+  r.tpb = kPairs / CT;
+  r.zblocks = (int)ceil_div(T, r.tpb);
+  int NB = kStageLds / (CT * (D + 1 + M));
+  if (NB > 32) NB = 32;
+  if (NB < 1) NB = 1;
+  r.NB = NB;
+  r.lds_coef = (size_t)NB * CT * (D + 1 + M) * sizeof(float);
+  return r;
 }
 
 template <class K>
@@ -240,14 +273,31 @@ int gmp_symmetric_contraction_fwd_f32(int64_t n_nodes, int channels, int dim, in
   GMP_CHECK_ARG(n_nodes >= 0 && shape_ok(channels, dim, rows, n_terms));
   if (n_nodes == 0) return GMP_OK;  // (an empty batch's x / out may be NULL)
   GMP_CHECK_ARG(plan && x && out && (n_terms == 0 || coef));
-  const int CT = channels < kMaxCT ? channels : kMaxCT;
-  const size_t smem = (size_t)kSC * row_stride(dim) * sizeof(float);
+  const Route r = route_of(n_nodes, channels, dim, rows, n_terms);
   int rc;
-  if ((rc = allow_smem(sc_fwd_kernel, smem))) return rc;
-  sc_fwd_kernel<<<dim3(node_blocks(n_nodes, channels, CT), (unsigned)ceil_div(channels, CT)), kSC,
-                  smem, as_stream(stream)>>>(n_nodes, channels, dim, rows, n_terms, CT, plan, coef,
-                                             x, out);
+  if ((rc = allow_smem(sc_fwd_kernel, r.lds_fwd))) return rc;
+  sc_fwd_kernel<<<dim3(r.nblocks, (unsigned)r.ctiles), kSC, r.lds_fwd, as_stream(stream)>>>(
+      n_nodes, channels, dim, rows, n_terms, r.CT, plan, coef, x, out);
   return launch_status();
+}
+
+int gmp_sc_route(int64_t n_nodes, int channels, int dim, int rows, int n_terms,
+                 int64_t out[12]) {
+  GMP_CHECK_ARG(out && n_nodes >= 0 && shape_ok(channels, dim, rows, n_terms));
+  const Route r = route_of(n_nodes, channels, dim, rows, n_terms);
+  out[0] = r.CT;
+  out[1] = r.npb;
+  out[2] = r.ctiles;
+  out[3] = r.nblocks;
+  out[4] = (int64_t)r.lds_fwd;
+  out[5] = (int64_t)r.lds_dx;
+  out[6] = r.CTd;
+  out[7] = r.tpb;
+  out[8] = r.zblocks;
+  out[9] = r.NB;
+  out[10] = r.G;
+  out[11] = r.per;
+  return GMP_OK;
 }
 
 int gmp_symmetric_contraction_bwd_f32(int64_t n_nodes, int channels, int dim, int rows,
@@ -264,33 +314,20 @@ int gmp_symmetric_contraction_bwd_f32(int64_t n_nodes, int channels, int dim, in
     return GMP_OK;
   }
   GMP_CHECK_ARG(plan && x && gout && (n_terms == 0 || coef || !dx));
+  const Route r = route_of(n_nodes, channels, dim, rows, n_terms);
   int rc;
   if (dx) {
-    const int CT = channels < kMaxCT ? channels : kMaxCT;
-    const size_t smem = (size_t)2 * kSC * row_stride(dim) * sizeof(float);
-    if ((rc = allow_smem(sc_bwd_x_kernel, smem))) return rc;
-    sc_bwd_x_kernel<<<dim3(node_blocks(n_nodes, channels, CT), (unsigned)ceil_div(channels, CT)),
-                      kSC, smem, s>>>(n_nodes, channels, dim, rows, n_terms, CT, plan, coef, x,
-                                      gout, dx);
+    if ((rc = allow_smem(sc_bwd_x_kernel, r.lds_dx))) return rc;
+    sc_bwd_x_kernel<<<dim3(r.nblocks, (unsigned)r.ctiles), kSC, r.lds_dx, s>>>(
+        n_nodes, channels, dim, rows, n_terms, r.CT, plan, coef, x, gout, dx);
     if ((rc = launch_status())) return rc;
   }
   if (dcoef_partials && n_terms > 0) {
-    const int G = gmp_sc_groups(n_nodes);
-    const int64_t per = ceil_div(n_nodes, (int64_t)G);
-    int CT = kPairs / n_terms;  // channels per tile: all of a tile's pairs in one workgroup
-    if (CT > kMaxCT) CT = kMaxCT;
-    if (CT > channels) CT = channels;
-    if (CT < 1) CT = 1;
-    const int tpb = kPairs / CT;
-    int NB = kStageLds / (CT * (dim + 1 + rows));
-    if (NB > 32) NB = 32;
-    if (NB < 1) NB = 1;
-    const size_t smem = (size_t)NB * CT * (dim + 1 + rows) * sizeof(float);
-    if ((rc = allow_smem(sc_bwd_coef_kernel, smem))) return rc;
-    sc_bwd_coef_kernel<<<dim3((unsigned)G, (unsigned)ceil_div(channels, CT),
-                              (unsigned)ceil_div(n_terms, tpb)),
-                         kSC, smem, s>>>(n_nodes, channels, dim, rows, n_terms, CT, NB, per, plan,
-                                         x, gout, dcoef_partials);
+    if ((rc = allow_smem(sc_bwd_coef_kernel, r.lds_coef))) return rc;
+    sc_bwd_coef_kernel<<<dim3((unsigned)r.G, (unsigned)ceil_div(channels, r.CTd),
+                              (unsigned)r.zblocks),
+                         kSC, r.lds_coef, s>>>(n_nodes, channels, dim, rows, n_terms, r.CTd, r.NB,
+                                               r.per, plan, x, gout, dcoef_partials);
     if ((rc = launch_status())) return rc;
   }
   return GMP_OK;

@@ -199,6 +199,9 @@ SIGNATURES = {
     "gmp_ln_act_bwd_f32": (c_int, [c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp,
                                    c_vp, c_size, c_vp]),
     "gmp_sc_groups": (c_int, [c_i64]),
+    # the launch-decomposition query (host arithmetic only); an addition, the ABI version is
+    # unchanged
+    "gmp_sc_route": (c_int, [c_i64, c_int, c_int, c_int, c_int, ctypes.POINTER(c_i64)]),
     "gmp_symmetric_contraction_fwd_f32": (c_int, [c_i64, c_int, c_int, c_int, c_int, c_vp, c_vp,
                                                   c_vp, c_vp, c_vp]),
     "gmp_symmetric_contraction_bwd_f32": (c_int, [c_i64, c_int, c_int, c_int, c_int, c_vp, c_vp,

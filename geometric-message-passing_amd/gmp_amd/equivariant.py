@@ -1014,7 +1014,43 @@ def k8_plan(contractions, D, C, correlation):
     words = torch.tensor(terms, dtype=torch.int64)
     words = torch.where(words >= 2 ** 31, words - 2 ** 32, words)  # int32 bit patterns
     plan = torch.cat([torch.tensor(row_ptr + base + stride, dtype=torch.int64), words])
-    return plan.to(torch.int32), torch.tensor(gather, dtype=torch.int64)
+    plan = plan.to(torch.int32)
+    check_k8_plan(plan, M, D, C)
+    return plan, torch.tensor(gather, dtype=torch.int64)
+
+
+def check_k8_plan(plan, rows, D, C):
+    """Raise ValueError unless `plan` (int32 [row_ptr | out_base | out_stride | terms], gmp.h) is
+    one the K8 kernels can walk inside their buffers: torch.ops.gmp.symmetric_contraction_* trust
+    its contents (row_ptr bounds the term loop, the factor fields index the thread's D + 1 LDS
+    slots, the row field the staged g row, out_base / out_stride the output columns).  Host work,
+    once per module."""
+    M = int(rows)
+    if not (1 <= M <= _K8_MAX_ROWS and 1 <= D <= _K8_MAX_DIM and C >= 1):
+        raise ValueError(f"K8 plan: rows {M}, dim {D}, channels {C} outside 1..{_K8_MAX_ROWS}, "
+                         f"1..{_K8_MAX_DIM}, >= 1")
+    if plan.dtype != torch.int32 or plan.dim() != 1 or plan.numel() < 3 * M + 1:
+        raise ValueError("K8 plan: expected 1-D int32 of 3 rows + 1 + n_terms entries")
+    p = plan.detach().cpu().to(torch.int64)
+    T = p.numel() - (3 * M + 1)
+    row_ptr, base, stride = p[:M + 1], p[M + 1:2 * M + 1], p[2 * M + 1:3 * M + 1]
+    words = p[3 * M + 1:] & 0xffffffff  # the int32 bit patterns, unsigned
+    if int(row_ptr[0]) != 0 or int(row_ptr[M]) != T or bool((row_ptr[1:] < row_ptr[:-1]).any()):
+        raise ValueError(f"K8 plan: row_ptr must run from 0 to n_terms = {T} without decreasing")
+    filed = torch.repeat_interleave(torch.arange(M), row_ptr[1:] - row_ptr[:-1])
+    if not torch.equal(words >> 24, filed):
+        t = int(torch.nonzero((words >> 24) != filed)[0])
+        raise ValueError(f"K8 plan: term {t} carries row {int(words[t] >> 24)} but is filed under "
+                         f"row {int(filed[t])}")
+    for r in range(4):
+        f = (words >> (6 * r)) & 63
+        if bool((f > D).any()):
+            t = int(torch.nonzero(f > D)[0])
+            raise ValueError(f"K8 plan: factor {r} of term {t} is {int(f[t])} > D = {D}")
+    cols = (base[:, None] + stride[:, None] * torch.arange(C)[None, :]).reshape(-1)
+    if not torch.equal(cols.sort().values, torch.arange(M * C)):
+        raise ValueError(f"K8 plan: out_base + out_stride * c is not a bijection onto "
+                         f"[0, {M * C})")
 
 
 class SymmetricContraction(nn.Module):

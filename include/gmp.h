@@ -1056,6 +1056,16 @@ int gmp_xyz_norm_bwd_f32(int64_t rows, int64_t h, const float* vh, const float* 
  * the dense per-degree A_nu arguments and gmp_sc_monomials.)
  * ------------------------------------------------------------------------------------------ */
 int gmp_sc_groups(int64_t n_nodes);
+/* The launch decomposition the two entry points below use for these sizes (host arithmetic, and
+ * the very values the launches take; node blocks depend on the current device's CU count).
+ * out[0..5], forward and dx kernels: channels per tile CT = min(C, 16), nodes per pass 256 / CT,
+ * channel tiles, node blocks (grid-stride over nodes), dynamic LDS bytes of the forward, of dx.
+ * out[6..11], dcoef kernel: channels per tile CT_d = clamp(4096 / n_terms, 1, min(16, C)), terms
+ * per workgroup 4096 / CT_d, term blocks (0 at n_terms = 0: no launch), nodes staged per round,
+ * node groups (= gmp_sc_groups), nodes per group.  GMP_ERR_ARG for sizes the entry points
+ * refuse. */
+int gmp_sc_route(int64_t n_nodes, int channels, int dim, int rows, int n_terms,
+                 int64_t out[12]);
 int gmp_symmetric_contraction_fwd_f32(int64_t n_nodes, int channels, int dim, int rows,
                                       int n_terms, const int32_t* plan, const float* coef,
                                       const float* x, float* out, void* stream);
