@@ -9,19 +9,18 @@
 //   torsion (SphereNet): min over the in-neighbours k_n != i of j of atan2(b, a) mapped to
 //   (0, 2*pi], with plane1 = v_ji x v_jk, plane2 = v_ji x v_jkn, a = plane1.plane2,
 //   b = (plane1 x plane2).v_ji / |v_ji|.
-// The arithmetic reproduces the reference's torch CPU evaluation operation by operation:
-// torch.cross is a_i*b_j - a_j*b_i contracted to fma(a_i, b_j, -(a_j*b_i)); `(x*y).sum(-1)`
-// rounds each product then adds (((+0 + 0) + 1) + 2); `.norm(-1)` accumulates fma(x, x, acc);
-// `.pow(2).sum(-1).sqrt()` is products, ((0 + 1) + 2), sqrt.  This matters beyond the last ulp:
-// for k_n = k plane1 == plane2, and the sign of the contracted cross product's rounding
-// residual decides whether that candidate's torsion is ~1e-9 or 2*pi — the reference's
-// output depends on it, so the kernel follows it.
+// The arithmetic is gmp_triplet_geom.h's, each rounding stated there.  It follows the reference's
+// torch CPU evaluation: torch.cross is a_i*b_j - a_j*b_i contracted to fma(a_i, b_j, -(a_j*b_i));
+// `(x*y).sum(-1)` rounds each product then adds (((+0 + 0) + 1) + 2); `.norm(-1)` accumulates
+// fma(x, x, acc).  This matters beyond the last ulp: for k_n = k plane1 == plane2, and the sign of
+// the contracted cross product's rounding residual decides whether that candidate's torsion is
+// ~1e-9 or 2*pi — the reference's output depends on it, so the kernel follows it.  The two
+// `.pow(2).sum(-1).sqrt()` lengths depart from torch's products, ((0 + 1) + 2), sqrt: dist is
+// sqrt(fma(y, y, x x) + z z) and the torsion's |v_ji| is sqrt(fma(x, x, y y) + z z).
 #include "gmp_triplet_geom.h"
 
 namespace gmp {
 namespace {
-
-constexpr float kTwoPi = 6.283185307179586f;
 
 __global__ void triplet_count_kernel(const float* __restrict__ pos,
                                      const int64_t* __restrict__ ei, int64_t E,
@@ -35,7 +34,7 @@ __global__ void triplet_count_kernel(const float* __restrict__ pos,
     int64_t p, q;
     equal_range(asrc, r0, r1, i, p, q);
     counts[e] = (r1 - r0) - (q - p);
-    if (dist) dist[e] = len3(sub3(ld3(pos, i), ld3(pos, j)));
+    if (dist) dist[e] = dist_len3(sub3(ld3(pos, i), ld3(pos, j)));
   }
 }
 
@@ -75,12 +74,7 @@ __global__ __launch_bounds__(kFB) void triplet_fill_kernel(
   __syncthreads();
   const int64_t t_begin = s_off[0], t_end = s_off[nE];
   for (int64_t t = t_begin + tid; t < t_end; t += kFB) {
-    int lo = 0, hi = nE;  // largest local edge with s_off <= t
-    while (hi - lo > 1) {
-      const int m = (lo + hi) >> 1;
-      if (s_off[m] <= t) lo = m;
-      else hi = m;
-    }
+    const int lo = find_local_edge(s_off, nE, t);
     const int64_t e = e0 + lo;
     const int64_t i = s_i[lo], j = s_j[lo], r0 = s_r0[lo], r1 = s_r1[lo];
     const int64_t p = s_p[lo], q = s_q[lo];
@@ -100,30 +94,24 @@ __global__ __launch_bounds__(kFB) void triplet_fill_kernel(
         u = sub3(pj, pi);
         v = sub3(pk, pi);
       }
-      angle[t] = atan2f(norm3(cross3(u, v)), dot3(u, v));
+      angle[t] = atan2f(norm3(cross3(u, v)), dot3_sum(u, v));
     }
     if (torsion) {
       const V3 vji = sub3(pi, pj);
-      const V3 vj0 = sub3(pk, pj);
-      const float dji = len3(vji);
-      const V3 plane1 = cross3(vji, vj0);
-      float best = 3.402823466e38f;  // torch_scatter min: identity FLT_MAX, NaN never wins
-      int64_t arg = -1;                // the winning candidate k_n (first among equal minima)
+      const float dji = torsion_len3(vji);
+      const V3 plane1 = cross3(vji, sub3(pk, pj));
+      float best = kNoTorsion;
+      int64_t arg = -1;  // the winning candidate k_n (first among equal minima)
       for (int64_t m = r0; m < r1; ++m) {
         const int64_t kn = asrc[m];
         if (kn == i) continue;
-        const V3 vjk = sub3(ld3(pos, kn), pj);
-        const V3 plane2 = cross3(vji, vjk);
-        const float a = dot3(plane1, plane2);
-        const float b = __fdiv_rn(dot3(cross3(plane1, plane2), vji), dji);
-        float t1 = atan2f(b, a);
-        if (t1 <= 0.f) t1 = __fadd_rn(t1, kTwoPi);
+        const float t1 = torsion_candidate(vji, plane1, dji, sub3(ld3(pos, kn), pj));
         if (t1 < best) {
           best = t1;
           arg = kn;
         }
       }
-      torsion[t] = best == 3.402823466e38f ? 0.f : best;
+      torsion[t] = best == kNoTorsion ? 0.f : best;
       if (torsion_kn) torsion_kn[t] = arg;
     }
   }
@@ -153,26 +141,17 @@ __global__ void triplet_geom_bwd_kernel(const float* __restrict__ pos,
       const V3 pv = ld3(pos, vtx), u = sub3(ld3(pos, ue), pv), v = sub3(ld3(pos, k), pv);
       V3 gu, gv;
       angle_bwd(u, v, g_angle ? g_angle[t] : 0.f, gu, gv);
-      float* r0 = rows + 3 * t;
-      float* r1 = rows + 3 * (T + t);
-      float* r2 = rows + 3 * (2 * T + t);
-      r0[0] = -(gu.x + gv.x); r0[1] = -(gu.y + gv.y); r0[2] = -(gu.z + gv.z);
-      r1[0] = gu.x; r1[1] = gu.y; r1[2] = gu.z;
-      r2[0] = gv.x; r2[1] = gv.y; r2[2] = gv.z;
+      st3(rows + 3 * t, neg3(acc3(gu, gv)));
+      st3(rows + 3 * (T + t), gu);
+      st3(rows + 3 * (2 * T + t), gv);
       node[t] = vtx;
       node[T + t] = ue;
       node[2 * T + t] = k;
     } else {
       const int64_t e = q - T;
       const int64_t j = ei[e], i = ei[E + e];
-      const V3 d = sub3(ld3(pos, i), ld3(pos, j));
-      const float len = len3(d);
-      const float g = g_dist ? g_dist[e] : 0.f;
-      const float s = (g != 0.f && len > 0.f) ? g / len : 0.f;
-      float* r0 = rows + 3 * (3 * T + e);
-      float* r1 = rows + 3 * (3 * T + E + e);
-      r0[0] = s * d.x; r0[1] = s * d.y; r0[2] = s * d.z;
-      r1[0] = -(s * d.x); r1[1] = -(s * d.y); r1[2] = -(s * d.z);
+      dist_bwd_row(sub3(ld3(pos, i), ld3(pos, j)), g_dist ? g_dist[e] : 0.f,
+                   rows + 3 * (3 * T + e), rows + 3 * (3 * T + E + e));
       node[3 * T + e] = i;
       node[3 * T + E + e] = j;
     }
@@ -226,12 +205,8 @@ __global__ void triplet_geom_bwd2_kernel(const float* __restrict__ pos,
       const int64_t j = ei[e], i = ei[E + e];
       const D3 d = dd3(sub3(ld3(pos, i), ld3(pos, j)));
       const D3 dd = dd3(sub3(ld3(a_pos, i), ld3(a_pos, j)));
-      const double len = sqrt(ddot(d, d));
-      const double g = g_dist ? (double)g_dist[e] : 0.0;
-      const double dlen = len > 0.0 ? ddot(d, dd) / len : 0.0;
-      D3 h{0.0, 0.0, 0.0};
-      if (g != 0.0 && len > 0.0)
-        h = dadd(dscale(g / len, dd), dscale(-g * dlen / (len * len), d));
+      D3 h;
+      const double dlen = dist_bwd2(d, dd, g_dist ? (double)g_dist[e] : 0.0, h);
       if (gg_dist) gg_dist[e] = (float)dlen;
       st3(rows + 3 * (3 * T + e), h);
       st3(rows + 3 * (3 * T + E + e), dscale(-1.0, h));
@@ -243,17 +218,10 @@ __global__ void triplet_geom_bwd2_kernel(const float* __restrict__ pos,
 
 // Backward of the SphereNet torsion w.r.t. pos (spherenet_layer.py:535-559 under autograd): the
 // scatter-min routes the gradient to the winning candidate k_n (torch_scatter's arg), whose
-// torsion1 = atan2(b, a) with u = p_i - p_j, v = p_k - p_j, w = p_kn - p_j,
-//   P = u x v, Q = u x w, a = P.Q, R = P x Q, c = R.u, L = |u|, b = c / L
-// (the 2 pi shift of torsion1 <= 0 has unit derivative).  Reverse mode:
-//   ga = -g b / (a^2 + b^2), gb = g a / (a^2 + b^2), gc = gb / L, gL = -gb c / L^2;
-//   gu = gL u / L + gc R;  gR = gc u;  gP = Q x gR + ga Q;  gQ = gR x P + ga P;
-//   gu += v x gP + w x gQ;  gv = gP x u;  gw = gQ x u;
-// rows [0, T) at i (gu), [T, 2T) at j (-(gu + gv + gw)), [2T, 3T) at k (gv), [3T, 4T) at k_n (gw);
-// triplets without a candidate (k_n < 0) write zero rows.
-__device__ __forceinline__ V3 xf(V3 a, V3 b) {
-  return V3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-}
+// torsion1 = atan2(b, a) is differentiated by torsion_bwd with u = p_i - p_j, v = p_k - p_j,
+// w = p_kn - p_j.  Rows [0, T) at i (gu), [T, 2T) at j (-(gu + gv + gw)), [2T, 3T) at k (gv),
+// [3T, 4T) at k_n (gw); triplets without a candidate (k_n < 0) and torsion_bwd's dead cases (an
+// edge of zero length, an exactly collinear triplet or winner) write zero rows.
 __global__ void triplet_torsion_bwd_kernel(const float* __restrict__ pos,
                                            const int64_t* __restrict__ ei, int64_t E,
                                            const int64_t* __restrict__ idx_kj,
@@ -267,33 +235,15 @@ __global__ void triplet_torsion_bwd_kernel(const float* __restrict__ pos,
     const int64_t j = ei[e], i = ei[E + e], k = ei[idx_kj[t]], kn = kn_of[t];
     const float g = g_tor[t];
     V3 gu{0.f, 0.f, 0.f}, gv{0.f, 0.f, 0.f}, gw{0.f, 0.f, 0.f};
-    if (kn >= 0 && g != 0.f) {
+    if (kn >= 0) {
       const V3 pj = ld3(pos, j);
-      const V3 u = sub3(ld3(pos, i), pj), v = sub3(ld3(pos, k), pj), w = sub3(ld3(pos, kn), pj);
-      const V3 P = cross3(u, v), Q = cross3(u, w), R = cross3(P, Q);
-      const float a = dot3(P, Q), c = dot3(R, u), L = len3(u);
-      const float b = c / L;
-      const float den = a * a + b * b;
-      const float ga = -g * b / den, gb = g * a / den;
-      const float gc = gb / L, gL = -gb * c / (L * L);
-      gu = V3{gL * u.x / L + gc * R.x, gL * u.y / L + gc * R.y, gL * u.z / L + gc * R.z};
-      const V3 gR{gc * u.x, gc * u.y, gc * u.z};
-      V3 gP = xf(Q, gR), gQ = xf(gR, P);
-      gP = V3{gP.x + ga * Q.x, gP.y + ga * Q.y, gP.z + ga * Q.z};
-      gQ = V3{gQ.x + ga * P.x, gQ.y + ga * P.y, gQ.z + ga * P.z};
-      const V3 a1 = xf(v, gP), a2 = xf(w, gQ);
-      gu = V3{gu.x + a1.x + a2.x, gu.y + a1.y + a2.y, gu.z + a1.z + a2.z};
-      gv = xf(gP, u);
-      gw = xf(gQ, u);
+      torsion_bwd(sub3(ld3(pos, i), pj), sub3(ld3(pos, k), pj), sub3(ld3(pos, kn), pj), g, gu,
+                  gv, gw);
     }
-    float* r = rows + 3 * t;
-    r[0] = gu.x; r[1] = gu.y; r[2] = gu.z;
-    r = rows + 3 * (T + t);
-    r[0] = -(gu.x + gv.x + gw.x); r[1] = -(gu.y + gv.y + gw.y); r[2] = -(gu.z + gv.z + gw.z);
-    r = rows + 3 * (2 * T + t);
-    r[0] = gv.x; r[1] = gv.y; r[2] = gv.z;
-    r = rows + 3 * (3 * T + t);
-    r[0] = gw.x; r[1] = gw.y; r[2] = gw.z;
+    st3(rows + 3 * t, gu);
+    st3(rows + 3 * (T + t), neg3(acc3(acc3(gu, gv), gw)));
+    st3(rows + 3 * (2 * T + t), gv);
+    st3(rows + 3 * (3 * T + t), gw);
     node[t] = i;
     node[T + t] = j;
     node[2 * T + t] = k;

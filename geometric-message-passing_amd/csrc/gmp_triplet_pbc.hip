@@ -2,7 +2,7 @@
 // include/gmp.h next to K11).  An edge is e = (j -> i, S_e) with the K9p vector
 // vec_e = (pos[j] - pos[i]) + t_e; its triplets are the entries kj = (k -> j, S_kj) of j's
 // in-adjacency except the reverse images of e (k == i and S_kj == -S_e, an integer compare);
-//   dist[e] = len3(vec_e),  angle[t] = atan2(|u x v|, u.v),  u = vec_ji, v = u + vec_kj
+//   dist[e] = dist_len3(vec_e),  angle[t] = atan2(|u x v|, u.v),  u = vec_ji, v = u + vec_kj
 // (v: the image of k relative to i).  The geometry is a function of the per-edge vectors only,
 // so the backward kernels work in edge-vector form: they take vec (E, 3) and write per-triplet
 // and per-edge rows that are summed per edge over CSRs the model already holds (no node[] array,
@@ -22,15 +22,6 @@ __device__ __forceinline__ I3 ldi3(const int32_t* __restrict__ p, int64_t a) {
 // the entry's shift is the negative of s (s of the edge whose reverse image is excluded)
 __device__ __forceinline__ bool is_neg(I3 a, I3 s) {
   return a.x == -s.x && a.y == -s.y && a.z == -s.z;
-}
-
-// |d| with the rounding of K11's dist as triplet_count_kernel is compiled (its dot3 contracts to
-// fma(y, y, x x) + z z), pinned here so that a graph with all shifts zero reproduces K11's dist
-// bit for bit whatever the compiler makes of this kernel's schedule.
-__device__ __forceinline__ float len3_k11(V3 a) {
-#pragma clang fp contract(off)
-  const float xx = a.x * a.x, zz = a.z * a.z;
-  return __fsqrt_rn(__builtin_fmaf(a.y, a.y, xx) + zz);
 }
 
 // counts[e] = in-degree(j) - #{entries (i -> j, -S_e)}: equal_range on source i, then a scan of
@@ -53,7 +44,7 @@ __global__ void triplet_count_pbc_kernel(const float* __restrict__ vec,
     int64_t excluded = 0;
     for (int64_t m = p; m < q; ++m) excluded += is_neg(ldi3(sidx, aeid[m]), s) ? 1 : 0;
     counts[e] = (r1 - r0) - excluded;
-    if (dist) dist[e] = len3_k11(ld3(vec, e));
+    if (dist) dist[e] = dist_len3(ld3(vec, e));
   }
 }
 
@@ -95,12 +86,7 @@ __global__ __launch_bounds__(kFBp) void triplet_fill_pbc_kernel(
   __syncthreads();
   const int64_t t_begin = s_off[0], t_end = s_off[nE];
   for (int64_t t = t_begin + tid; t < t_end; t += kFBp) {
-    int lo = 0, hi = nE;  // largest local edge with s_off <= t
-    while (hi - lo > 1) {
-      const int m = (lo + hi) >> 1;
-      if (s_off[m] <= t) lo = m;
-      else hi = m;
-    }
+    const int lo = find_local_edge(s_off, nE, t);
     const int64_t e = e0 + lo;
     const int64_t r0 = s_r0[lo], r1 = s_r1[lo], p = s_p[lo], q = s_q[lo];
     int64_t slot = r0 + (t - s_off[lo]);
@@ -120,7 +106,7 @@ __global__ __launch_bounds__(kFBp) void triplet_fill_pbc_kernel(
     idx_ji[t] = e;
     if (angle) {
       const V3 u = ld3(vec, e), v = add3(u, ld3(vec, kj));
-      angle[t] = atan2f(norm3(cross3(u, v)), dot3(u, v));
+      angle[t] = atan2f(norm3(cross3(u, v)), dot3_sum(u, v));
     }
   }
 }
@@ -143,18 +129,11 @@ __global__ void triplet_vec_bwd_kernel(const float* __restrict__ vec, int64_t E,
       const V3 u = ld3(vec, idx_ji[t]), v = add3(u, ld3(vec, idx_kj[t]));
       V3 gu, gv;
       angle_bwd(u, v, g_angle ? g_angle[t] : 0.f, gu, gv);
-      float* r0 = rows + 3 * t;
-      float* r1 = rows + 3 * (T + t);
-      r0[0] = gu.x + gv.x; r0[1] = gu.y + gv.y; r0[2] = gu.z + gv.z;
-      r1[0] = gv.x; r1[1] = gv.y; r1[2] = gv.z;
+      st3(rows + 3 * t, acc3(gu, gv));
+      st3(rows + 3 * (T + t), gv);
     } else {
       const int64_t e = q - T;
-      const V3 d = ld3(vec, e);
-      const float len = len3(d);
-      const float g = g_dist ? g_dist[e] : 0.f;
-      const float s = (g != 0.f && len > 0.f) ? g / len : 0.f;
-      float* r = rows + 3 * (2 * T + e);
-      r[0] = s * d.x; r[1] = s * d.y; r[2] = s * d.z;
+      dist_bwd_row(ld3(vec, e), g_dist ? g_dist[e] : 0.f, rows + 3 * (2 * T + e));
     }
   }
 }
@@ -191,12 +170,8 @@ __global__ void triplet_vec_bwd2_kernel(const float* __restrict__ vec, int64_t E
     } else {
       const int64_t e = q - T;
       const D3 d = dd3(ld3(vec, e)), dd = dd3(ld3(a_vec, e));
-      const double len = sqrt(ddot(d, d));
-      const double g = g_dist ? (double)g_dist[e] : 0.0;
-      const double dlen = len > 0.0 ? ddot(d, dd) / len : 0.0;
-      D3 h{0.0, 0.0, 0.0};
-      if (g != 0.0 && len > 0.0)
-        h = dadd(dscale(g / len, dd), dscale(-g * dlen / (len * len), d));
+      D3 h;
+      const double dlen = dist_bwd2(d, dd, g_dist ? (double)g_dist[e] : 0.0, h);
       if (gg_dist) gg_dist[e] = (float)dlen;
       st3(rows + 3 * (2 * T + e), h);
     }
@@ -207,23 +182,9 @@ __global__ void triplet_vec_bwd2_kernel(const float* __restrict__ vec, int64_t E
 // SphereNet's angle and torsion on the lists above (the K11p contract, "SphereNet" part): for
 // triplet t of edge e, u = 0 - vec_e, v = vec[idx_kj[t]], angle at j; the torsion is the minimum
 // over the triplets t' of the same edge (w = vec[idx_kj[t']]) of atan2(b, a) mapped to (0, 2 pi].
-// With zero shifts this is triplet_fill_kernel's mode 0 bit for bit, so the two places where
-// that kernel as compiled for gfx950 departs from its source's operation order are pinned here
-// (read from its assembly): the sums of dot3 stay uncontracted, and |u| of the torsion is
-// sqrt(fma(x, x, y y) + z z).  cross3 / norm3 are explicit fma chains and compile as written.
-constexpr float kTwoPi = 6.283185307179586f;
-
-__device__ __forceinline__ float dot3_k11(V3 a, V3 b) {
-#pragma clang fp contract(off)
-  const float xx = a.x * b.x, yy = a.y * b.y, zz = a.z * b.z;
-  return ((0.f + xx) + yy) + zz;
-}
-__device__ __forceinline__ float len3_tor_k11(V3 a) {
-#pragma clang fp contract(off)
-  const float yy = a.y * a.y, zz = a.z * a.z;
-  return __fsqrt_rn(__builtin_fmaf(a.x, a.x, yy) + zz);
-}
-
+// With zero shifts this is triplet_fill_kernel's mode 0 bit for bit: both call the same helpers
+// of gmp_triplet_geom.h, whose roundings are explicit.
+//
 // A thread per triplet; it walks the candidate range [offs[e], offs[e+1]) of its edge (K11's
 // form).  plane2 is recomputed per pair: 9 of the ~110 VALU operations of a pair, the rest is
 // the division and atan2f.
@@ -233,65 +194,28 @@ __global__ void triplet_dat_pbc_kernel(const float* __restrict__ vec,
                                        const int64_t* __restrict__ offs, int64_t T,
                                        float* __restrict__ angle, float* __restrict__ torsion,
                                        int64_t* __restrict__ torsion_arg) {
-#pragma clang fp contract(off)
   const V3 zero{0.f, 0.f, 0.f};
   for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < T;
        t += (int64_t)gridDim.x * blockDim.x) {
     const int64_t e = idx_ji[t];
     const V3 u = sub3(zero, ld3(vec, e)), v = ld3(vec, idx_kj[t]);
     const V3 plane1 = cross3(u, v);
-    if (angle) angle[t] = atan2f(norm3(plane1), dot3_k11(u, v));
+    if (angle) angle[t] = atan2f(norm3(plane1), dot3_sum(u, v));
     if (!torsion) continue;
-    const float dji = len3_tor_k11(u);
-    float best = 3.402823466e38f;  // torch_scatter min: identity FLT_MAX, NaN never wins
-    int64_t arg = -1;                // first among equal minima
+    const float dji = torsion_len3(u);
+    float best = kNoTorsion;
+    int64_t arg = -1;  // first among equal minima
     const int64_t o1 = offs[e + 1];
     for (int64_t c = offs[e]; c < o1; ++c) {
-      const V3 w = ld3(vec, idx_kj[c]);
-      const V3 plane2 = cross3(u, w);
-      const float a = dot3_k11(plane1, plane2);
-      const float b = dot3_k11(cross3(plane1, plane2), u) / dji;
-      float t1 = atan2f(b, a);
-      if (t1 <= 0.f) t1 = t1 + kTwoPi;
+      const float t1 = torsion_candidate(u, plane1, dji, ld3(vec, idx_kj[c]));
       if (t1 < best) {
         best = t1;
         arg = c;
       }
     }
-    torsion[t] = best == 3.402823466e38f ? 0.f : best;
+    torsion[t] = best == kNoTorsion ? 0.f : best;
     torsion_arg[t] = arg;
   }
-}
-
-__device__ __forceinline__ V3 xf3(V3 a, V3 b) {
-  return V3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-}
-__device__ __forceinline__ V3 acc3(V3 a, V3 b) { return V3{a.x + b.x, a.y + b.y, a.z + b.z}; }
-
-// Reverse mode of one candidate's t1 = atan2(b, a) scaled by g (the derivation is the comment
-// above triplet_torsion_bwd_kernel in gmp_triplet.hip; the 2 pi shift has unit derivative).
-// Dead cases, zero outputs: g == 0, a^2 + b^2 == 0 (an exactly collinear triplet, a candidate
-// exactly parallel to u) and |u| == 0.
-__device__ __forceinline__ void torsion_bwd(V3 u, V3 v, V3 w, float g, V3& gu, V3& gv, V3& gw) {
-  const V3 z{0.f, 0.f, 0.f};
-  gu = z; gv = z; gw = z;
-  if (g == 0.f) return;
-  const V3 P = cross3(u, v), Q = cross3(u, w), R = cross3(P, Q);
-  const float a = dot3(P, Q), c = dot3(R, u), L = len3(u);
-  if (!(L > 0.f)) return;
-  const float b = c / L;
-  const float den = a * a + b * b;
-  if (!(den > 0.f)) return;
-  const float ga = -g * b / den, gb = g * a / den;
-  const float gc = gb / L, gL = -gb * c / (L * L);
-  gu = V3{gL * u.x / L + gc * R.x, gL * u.y / L + gc * R.y, gL * u.z / L + gc * R.z};
-  const V3 gR{gc * u.x, gc * u.y, gc * u.z};
-  V3 gP = xf3(Q, gR), gQ = xf3(gR, P);
-  gP = V3{gP.x + ga * Q.x, gP.y + ga * Q.y, gP.z + ga * Q.z};
-  gQ = V3{gQ.x + ga * P.x, gQ.y + ga * P.y, gQ.z + ga * P.z};
-  gu = acc3(gu, acc3(xf3(v, gP), xf3(w, gQ)));
-  gv = xf3(gP, u);
-  gw = xf3(gQ, u);
 }
 
 // First backward of dist, angle and torsion in edge-vector form.  rows (2T + E, 3) in the layout
@@ -332,18 +256,11 @@ __global__ void triplet_dat_vec_bwd_kernel(const float* __restrict__ vec, int64_
           gv = acc3(gv, tw);
         }
       }
-      float* r0 = rows + 3 * t;
-      float* r1 = rows + 3 * (T + t);
-      r0[0] = -gu.x; r0[1] = -gu.y; r0[2] = -gu.z;
-      r1[0] = gv.x; r1[1] = gv.y; r1[2] = gv.z;
+      st3(rows + 3 * t, neg3(gu));
+      st3(rows + 3 * (T + t), gv);
     } else {
       const int64_t e = q - T;
-      const V3 d = ld3(vec, e);
-      const float len = len3(d);
-      const float g = g_dist ? g_dist[e] : 0.f;
-      const float s = (g != 0.f && len > 0.f) ? g / len : 0.f;
-      float* r = rows + 3 * (2 * T + e);
-      r[0] = s * d.x; r[1] = s * d.y; r[2] = s * d.z;
+      dist_bwd_row(ld3(vec, e), g_dist ? g_dist[e] : 0.f, rows + 3 * (2 * T + e));
     }
   }
 }

@@ -20,9 +20,8 @@ import torch
 from torch.nn import Embedding, Linear
 
 from . import ops
-from .graph import edge_shift
 from .spherenet import ResidualLayer, basis_tables, glorot_orthogonal, swish
-from .triplets import dimenet_angles, triplet_offsets
+from .triplets import dimenet_angles, model_geometry_inputs, triplet_offsets
 
 
 def _activation(act):
@@ -242,25 +241,11 @@ class DimeNetPPModel(torch.nn.Module):
         return ops.DimeTripletProjFn.apply(sbe, angle, idx_kj, self.sbf.pref, n, k, L, *weights)
 
     def forward(self, batch):
-        shift_idx = getattr(batch, "edge_shift_idx", None)
-        shift = None
-        if shift_idx is not None:
-            if not getattr(self, "periodic", False):
-                raise NotImplementedError(
-                    "DimeNetPPModel: periodic shifts (edge_shift_idx) need a model built (or "
-                    "set) with periodic=True: K11's open-boundary triplets take no periodic "
-                    "images")
-            shift = edge_shift(batch)  # ValueError without batch.cell, before any device work
-        z, pos, edge_index = batch.atoms, batch.pos, batch.edge_index
-        ops._need_cuda(z, pos, edge_index, batch.batch)
         twice = self._twice()
-        if torch.is_grad_enabled() and not twice:  # forces / stress yes, training through them no
-            if pos.requires_grad:
-                pos = ops.FirstOrderOnlyFn.apply(pos)
-            if shift is not None and shift.requires_grad:
-                shift = ops.FirstOrderOnlyFn.apply(shift)
+        pos, shift, shift_idx = model_geometry_inputs("DimeNetPPModel", self, batch, not twice)
+        z = batch.atoms
         dist, angle, i, j, _, _, _, idx_kj, idx_ji = dimenet_angles(
-            pos, edge_index, z.size(0), twice_differentiable=twice, shift=shift,
+            pos, batch.edge_index, z.size(0), twice_differentiable=twice, shift=shift,
             shift_idx=shift_idx)
         return self.forward_from_geometry(z, dist, angle, i, j, idx_kj, idx_ji, batch.batch,
                                           num_graphs=getattr(batch, "num_graphs", None))

@@ -26,8 +26,7 @@ from torch import nn
 from torch.nn import Embedding, Linear
 
 from . import ops
-from .graph import edge_shift
-from .triplets import xyz_to_dat, triplet_offsets
+from .triplets import model_geometry_inputs, triplet_offsets, xyz_to_dat
 
 
 def swish(x):
@@ -369,25 +368,11 @@ class SphereNetModel(torch.nn.Module):
             uv.reset_parameters()
 
     def forward(self, batch_data):
-        shift_idx = getattr(batch_data, "edge_shift_idx", None)
-        shift = None
-        if shift_idx is not None:
-            if not getattr(self, "periodic", False):
-                raise NotImplementedError(
-                    "SphereNetModel: periodic shifts (edge_shift_idx) need a model built (or "
-                    "set) with periodic=True: K11's open-boundary triplets take no periodic "
-                    "images")
-            shift = edge_shift(batch_data)  # ValueError without batch.cell, before device work
-        z, pos, batch = batch_data.atoms, batch_data.pos, batch_data.batch
-        edge_index = batch_data.edge_index
-        ops._need_cuda(z, pos, edge_index, batch)
-        if torch.is_grad_enabled():  # forces / stress yes, training through them no
-            if pos.requires_grad:
-                pos = ops.FirstOrderOnlyFn.apply(pos)
-            if shift is not None and shift.requires_grad:
-                shift = ops.FirstOrderOnlyFn.apply(shift)
+        pos, shift, shift_idx = model_geometry_inputs("SphereNetModel", self, batch_data, True)
+        z, batch = batch_data.atoms, batch_data.batch
         dist, angle, torsion, i, j, idx_kj, idx_ji = xyz_to_dat(
-            pos, edge_index, z.size(0), use_torsion=True, shift=shift, shift_idx=shift_idx)
+            pos, batch_data.edge_index, z.size(0), use_torsion=True, shift=shift,
+            shift_idx=shift_idx)
         return self.forward_from_geometry(z, dist, angle, torsion, i, j, idx_kj, idx_ji, batch,
                                           num_graphs=getattr(batch_data, "num_graphs", None))
 

@@ -24,6 +24,7 @@ summed over cached CSRs; pos and the cell are reached through the recorded linea
 import torch
 
 from . import _lib, ops
+from .graph import edge_shift
 
 
 def adjacency_by_target(edge_index, num_nodes):
@@ -36,6 +37,28 @@ def adjacency_by_target(edge_index, num_nodes):
     return by_dst.rowptr, src[order], order
 
 
+def _cot(g):
+    """A cotangent for a kernel: contiguous float32, or None kept as None (a NULL pointer)."""
+    return ops._f32c(g) if g is not None else None
+
+
+def _enumerate(ei, num_nodes, count, fill):
+    """The enumeration shared by K11 and K11p: adjacency by target, count(adj, counts, stream),
+    the triplet offsets, the one host read of T, the lists, fill(adj, offs, T, idx_kj, idx_ji,
+    stream).  -> idx_kj, idx_ji, offs, and what fill returns (the per-triplet arrays it made)."""
+    E, dev = ei.shape[1], ei.device
+    adj = adjacency_by_target(ei, num_nodes)
+    counts = torch.empty(E, dtype=torch.int64, device=dev)
+    s = ops._stream()
+    count(adj, counts, s)
+    offs = torch.zeros(E + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(counts, 0, out=offs[1:])
+    T = int(offs[-1].item()) if E else 0
+    idx_kj = torch.empty(T, dtype=torch.int64, device=dev)
+    idx_ji = torch.empty(T, dtype=torch.int64, device=dev)
+    return idx_kj, idx_ji, offs, fill(adj, offs, T, idx_kj, idx_ji, s)
+
+
 def _run(pos, edge_index, num_nodes, mode, want_angle, want_torsion, want_dist, want_kn=False):
     lib = _lib.load()
     ei = ops._i64c(edge_index)
@@ -46,45 +69,60 @@ def _run(pos, edge_index, num_nodes, mode, want_angle, want_torsion, want_dist, 
     dev = ei.device
     E = ei.shape[1]
     N = int(num_nodes)
-    rowptr, asrc, aeid = adjacency_by_target(ei, N)
-    counts = torch.empty(E, dtype=torch.int64, device=dev)
     dist = torch.empty(E, dtype=torch.float32, device=dev) if want_dist else None
-    s = ops._stream()
-    ops.check(lib.gmp_triplet_count(ops._p(pos), ops._p(ei), E, N, ops._p(rowptr), ops._p(asrc),
-                                    ops._p(counts), ops._p(dist), s), "gmp_triplet_count")
-    offs = torch.zeros(E + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(counts, 0, out=offs[1:])
-    T = int(offs[-1].item()) if E else 0
-    idx_kj = torch.empty(T, dtype=torch.int64, device=dev)
-    idx_ji = torch.empty(T, dtype=torch.int64, device=dev)
-    angle = torch.empty(T, dtype=torch.float32, device=dev) if want_angle else None
-    torsion = torch.empty(T, dtype=torch.float32, device=dev) if want_torsion else None
-    kn = torch.empty(T, dtype=torch.int64, device=dev) if want_kn else None
-    ops.check(lib.gmp_triplet_fill_f32(ops._p(pos), ops._p(ei), E, N, ops._p(rowptr),
-                                       ops._p(asrc), ops._p(aeid), ops._p(offs), T, mode,
-                                       ops._p(idx_kj), ops._p(idx_ji), ops._p(angle),
-                                       ops._p(torsion), ops._p(kn), s), "gmp_triplet_fill_f32")
+
+    def count(adj, counts, s):
+        ops.check(lib.gmp_triplet_count(ops._p(pos), ops._p(ei), E, N, ops._p(adj[0]),
+                                        ops._p(adj[1]), ops._p(counts), ops._p(dist), s),
+                  "gmp_triplet_count")
+
+    def fill(adj, offs, T, idx_kj, idx_ji, s):
+        angle = torch.empty(T, dtype=torch.float32, device=dev) if want_angle else None
+        torsion = torch.empty(T, dtype=torch.float32, device=dev) if want_torsion else None
+        kn = torch.empty(T, dtype=torch.int64, device=dev) if want_kn else None
+        ops.check(lib.gmp_triplet_fill_f32(ops._p(pos), ops._p(ei), E, N, *map(ops._p, adj),
+                                           ops._p(offs), T, mode, ops._p(idx_kj), ops._p(idx_ji),
+                                           ops._p(angle), ops._p(torsion), ops._p(kn), s),
+                  "gmp_triplet_fill_f32")
+        return angle, torsion, kn
+
+    idx_kj, idx_ji, _, (angle, torsion, kn) = _enumerate(ei, N, count, fill)
     if want_kn:
         return dist, angle, torsion, idx_kj, idx_ji, kn
     return dist, angle, torsion, idx_kj, idx_ji
 
 
+def _geom_forward(ctx, pos, edge_index, num_nodes, mode, use_torsion):
+    """The forward of TripletGeomFn and TripletGeom2Fn: torsion and its winners k_n are empty
+    without use_torsion."""
+    res = _run(pos, edge_index, num_nodes, mode, True, use_torsion, True, use_torsion)
+    dist, angle, torsion, idx_kj, idx_ji = res[:5]
+    kn = res[5] if use_torsion else None
+    if torsion is None:
+        torsion = torch.empty(0, dtype=torch.float32, device=dist.device)
+        kn = torch.empty(0, dtype=torch.int64, device=dist.device)
+    ctx.save_for_backward(pos, ops._i64c(edge_index), idx_kj, idx_ji, kn)
+    ctx.mode, ctx.n, ctx.use_torsion = mode, int(num_nodes), use_torsion
+    ctx.mark_non_differentiable(idx_kj, idx_ji)
+    return dist, angle, torsion, idx_kj, idx_ji
+
+
+def _geom_bwd_rows(pos, ei, idx_kj, idx_ji, g_dist, g_angle, mode, spare=0):
+    """rows (3T + 2E + spare, 3) and node of gmp_triplet_geom_bwd_f32; the spare rows at the end
+    are left for the torsion's."""
+    E, T = ei.shape[1], idx_kj.numel()
+    rows, node = _geom_rows(3 * T + 2 * E + spare, pos.device)
+    gd, ga, p32 = _cot(g_dist), _cot(g_angle), ops._f32c(pos)
+    ops.check(_lib.load().gmp_triplet_geom_bwd_f32(
+        ops._p(p32), ops._p(ei), E, ops._p(idx_kj), ops._p(idx_ji), T, mode, ops._p(gd),
+        ops._p(ga), ops._p(rows), ops._p(node), ops._stream()), "gmp_triplet_geom_bwd_f32")
+    return rows, node
+
+
 class TripletGeomFn(torch.autograd.Function):
     """(dist (E), angle (T), torsion (T, or empty without use_torsion), idx_kj, idx_ji) with the
     backward of dist, angle and torsion w.r.t. pos."""
-
-    @staticmethod
-    def forward(ctx, pos, edge_index, num_nodes, mode, use_torsion):
-        res = _run(pos, edge_index, num_nodes, mode, True, use_torsion, True, use_torsion)
-        dist, angle, torsion, idx_kj, idx_ji = res[:5]
-        kn = res[5] if use_torsion else None
-        if torsion is None:
-            torsion = torch.empty(0, dtype=torch.float32, device=dist.device)
-            kn = torch.empty(0, dtype=torch.int64, device=dist.device)
-        ctx.save_for_backward(pos, ops._i64c(edge_index), idx_kj, idx_ji, kn)
-        ctx.mode, ctx.n, ctx.use_torsion = mode, int(num_nodes), use_torsion
-        ctx.mark_non_differentiable(idx_kj, idx_ji)
-        return dist, angle, torsion, idx_kj, idx_ji
+    forward = staticmethod(_geom_forward)
 
     @staticmethod
     def backward(ctx, g_dist, g_angle, g_torsion, _g1, _g2):
@@ -92,29 +130,16 @@ class TripletGeomFn(torch.autograd.Function):
         if not ctx.needs_input_grad[0]:
             return None, None, None, None, None
         E, T = ei.shape[1], idx_kj.numel()
-        dev = pos.device
         p32 = ops._f32c(pos.detach())
         nt = 4 * T if (ctx.use_torsion and g_torsion is not None) else 0
-        rows = torch.empty((3 * T + 2 * E + nt, 3), dtype=torch.float32, device=dev)
-        node = torch.empty(3 * T + 2 * E + nt, dtype=torch.int64, device=dev)
-        gd = ops._f32c(g_dist) if g_dist is not None else None
-        ga = ops._f32c(g_angle) if g_angle is not None else None
-        lib = _lib.load()
-        s = ops._stream()
-        ops.check(lib.gmp_triplet_geom_bwd_f32(ops._p(p32), ops._p(ei), E, ops._p(idx_kj),
-                                               ops._p(idx_ji), T, ctx.mode, ops._p(gd),
-                                               ops._p(ga), ops._p(rows), ops._p(node), s),
-                  "gmp_triplet_geom_bwd_f32")
+        rows, node = _geom_bwd_rows(p32, ei, idx_kj, idx_ji, g_dist, g_angle, ctx.mode, nt)
         if nt:
             m = 3 * T + 2 * E
-            ops.check(lib.gmp_triplet_torsion_bwd_f32(ops._p(p32), ops._p(ei), E,
-                                                      ops._p(idx_kj), ops._p(idx_ji),
-                                                      ops._p(kn), T,
-                                                      ops._p(ops._f32c(g_torsion)),
-                                                      ops._p(rows[m:]), ops._p(node[m:]), s),
-                      "gmp_triplet_torsion_bwd_f32")
-        g_pos, _ = ops.segment_reduce(rows, ops.CSR(node, ctx.n), "sum")
-        return g_pos.to(pos.dtype), None, None, None, None
+            ops.check(_lib.load().gmp_triplet_torsion_bwd_f32(
+                ops._p(p32), ops._p(ei), E, ops._p(idx_kj), ops._p(idx_ji), ops._p(kn), T,
+                ops._p(_cot(g_torsion)), ops._p(rows[m:]), ops._p(node[m:]), ops._stream()),
+                "gmp_triplet_torsion_bwd_f32")
+        return _rows_to_pos(rows, node, ctx.n, pos.dtype), None, None, None, None
 
 
 class TripletGeom2Fn(torch.autograd.Function):
@@ -123,17 +148,12 @@ class TripletGeom2Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pos, edge_index, num_nodes, mode):
-        dist, angle, _, idx_kj, idx_ji = _run(pos, edge_index, num_nodes, mode, True, False, True)
-        ctx.save_for_backward(pos, ops._i64c(edge_index), idx_kj, idx_ji)
-        ctx.mode, ctx.n = mode, int(num_nodes)
-        ctx.mark_non_differentiable(idx_kj, idx_ji)
         ctx.set_materialize_grads(False)
-        torsion = torch.empty(0, dtype=torch.float32, device=dist.device)
-        return dist, angle, torsion, idx_kj, idx_ji
+        return _geom_forward(ctx, pos, edge_index, num_nodes, mode, False)
 
     @staticmethod
     def backward(ctx, g_dist, g_angle, _g0, _g1, _g2):
-        pos, ei, idx_kj, idx_ji = ctx.saved_tensors
+        pos, ei, idx_kj, idx_ji, _ = ctx.saved_tensors
         if not ctx.needs_input_grad[0] or (g_dist is None and g_angle is None):
             return None, None, None, None
         g_pos = TripletGeomBwdFn.apply(pos, ei, idx_kj, idx_ji, g_dist, g_angle, ctx.mode, ctx.n)
@@ -162,14 +182,7 @@ class TripletGeomBwdFn(torch.autograd.Function):
     def forward(ctx, pos, ei, idx_kj, idx_ji, g_dist, g_angle, mode, n):
         ctx.save_for_backward(pos, ei, idx_kj, idx_ji, g_dist, g_angle)
         ctx.mode, ctx.n = mode, n
-        E, T = ei.shape[1], idx_kj.numel()
-        rows, node = _geom_rows(3 * T + 2 * E, pos.device)
-        gd = ops._f32c(g_dist) if g_dist is not None else None
-        ga = ops._f32c(g_angle) if g_angle is not None else None
-        p32 = ops._f32c(pos)
-        ops.check(_lib.load().gmp_triplet_geom_bwd_f32(
-            ops._p(p32), ops._p(ei), E, ops._p(idx_kj), ops._p(idx_ji), T, mode, ops._p(gd),
-            ops._p(ga), ops._p(rows), ops._p(node), ops._stream()), "gmp_triplet_geom_bwd_f32")
+        rows, node = _geom_bwd_rows(pos, ei, idx_kj, idx_ji, g_dist, g_angle, mode)
         return _rows_to_pos(rows, node, n, pos.dtype)
 
     @staticmethod
@@ -182,8 +195,7 @@ class TripletGeomBwdFn(torch.autograd.Function):
         rows, node = _geom_rows(3 * T + 2 * E, dev)
         gg_d = torch.empty(E, dtype=torch.float32, device=dev)
         gg_a = torch.empty(T, dtype=torch.float32, device=dev)
-        gd = ops._f32c(g_dist) if g_dist is not None else None
-        ga = ops._f32c(g_angle) if g_angle is not None else None
+        gd, ga = _cot(g_dist), _cot(g_angle)
         p32, a32 = ops._f32c(pos), ops._f32c(a_pos)
         ops.check(_lib.load().gmp_triplet_geom_bwd2_f32(
             ops._p(p32), ops._p(ei), E, ops._p(idx_kj), ops._p(idx_ji), T, ctx.mode, ops._p(gd),
@@ -221,23 +233,22 @@ def _run_pbc(vec, edge_index, num_nodes, shift_idx, want_angle=True, want_dist=T
         f32 = torch.empty(0, dtype=torch.float32, device=dev)
         out = (f32 if want_dist else None, f32.clone() if want_angle else None, i64, i64.clone())
         return out + (torch.zeros(1, dtype=torch.int64, device=dev),) if want_offsets else out
-    rowptr, asrc, aeid = adjacency_by_target(ei, N)
-    counts = torch.empty(E, dtype=torch.int64, device=dev)
     dist = torch.empty(E, dtype=torch.float32, device=dev) if want_dist else None
-    s = ops._stream()
-    ops.check(lib.gmp_triplet_count_pbc(ops._p(vec), ops._p(ei), E, N, ops._p(rowptr),
-                                        ops._p(asrc), ops._p(aeid), ops._p(sidx), ops._p(counts),
-                                        ops._p(dist), s), "gmp_triplet_count_pbc")
-    offs = torch.zeros(E + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(counts, 0, out=offs[1:])
-    T = int(offs[-1].item())
-    idx_kj = torch.empty(T, dtype=torch.int64, device=dev)
-    idx_ji = torch.empty(T, dtype=torch.int64, device=dev)
-    angle = torch.empty(T, dtype=torch.float32, device=dev) if want_angle else None
-    ops.check(lib.gmp_triplet_fill_pbc_f32(ops._p(vec), ops._p(ei), E, N, ops._p(rowptr),
-                                           ops._p(asrc), ops._p(aeid), ops._p(sidx),
-                                           ops._p(offs), T, ops._p(idx_kj), ops._p(idx_ji),
-                                           ops._p(angle), s), "gmp_triplet_fill_pbc_f32")
+
+    def count(adj, counts, s):
+        ops.check(lib.gmp_triplet_count_pbc(ops._p(vec), ops._p(ei), E, N, *map(ops._p, adj),
+                                            ops._p(sidx), ops._p(counts), ops._p(dist), s),
+                  "gmp_triplet_count_pbc")
+
+    def fill(adj, offs, T, idx_kj, idx_ji, s):
+        angle = torch.empty(T, dtype=torch.float32, device=dev) if want_angle else None
+        ops.check(lib.gmp_triplet_fill_pbc_f32(ops._p(vec), ops._p(ei), E, N, *map(ops._p, adj),
+                                               ops._p(sidx), ops._p(offs), T, ops._p(idx_kj),
+                                               ops._p(idx_ji), ops._p(angle), s),
+                  "gmp_triplet_fill_pbc_f32")
+        return angle
+
+    idx_kj, idx_ji, offs, angle = _enumerate(ei, N, count, fill)
     if want_offsets:
         return dist, angle, idx_kj, idx_ji, offs
     return dist, angle, idx_kj, idx_ji
@@ -258,25 +269,26 @@ def _rows_to_vec(rows, idx_kj, idx_ji, E, dtype):
 def _vec_bwd(vec, idx_kj, idx_ji, g_dist, g_angle):
     E, T = vec.shape[0], idx_kj.numel()
     rows = torch.empty((2 * T + E, 3), dtype=torch.float32, device=vec.device)
-    gd = ops._f32c(g_dist) if g_dist is not None else None
-    ga = ops._f32c(g_angle) if g_angle is not None else None
+    gd, ga = _cot(g_dist), _cot(g_angle)
     ops.check(_lib.load().gmp_triplet_vec_bwd_f32(
         ops._p(ops._f32c(vec)), E, ops._p(idx_kj), ops._p(idx_ji), T, ops._p(gd), ops._p(ga),
         ops._p(rows), ops._stream()), "gmp_triplet_vec_bwd_f32")
     return _rows_to_vec(rows, idx_kj, idx_ji, E, vec.dtype)
 
 
+def _vec_geom_forward(ctx, vec, edge_index, num_nodes, shift_idx):
+    """The forward of TripletVecGeomFn and TripletVecGeom2Fn."""
+    dist, angle, idx_kj, idx_ji = _run_pbc(vec, edge_index, num_nodes, shift_idx)
+    ctx.save_for_backward(vec, idx_kj, idx_ji)
+    ctx.mark_non_differentiable(idx_kj, idx_ji)
+    ctx.set_materialize_grads(False)
+    return dist, angle, idx_kj, idx_ji
+
+
 class TripletVecGeomFn(torch.autograd.Function):
     """(dist (E), angle (T), idx_kj, idx_ji) of K11p from vec (E, 3) with the backward of dist and
     angle w.r.t. vec (gmp_triplet_vec_bwd_f32); once differentiable."""
-
-    @staticmethod
-    def forward(ctx, vec, edge_index, num_nodes, shift_idx):
-        dist, angle, idx_kj, idx_ji = _run_pbc(vec, edge_index, num_nodes, shift_idx)
-        ctx.save_for_backward(vec, idx_kj, idx_ji)
-        ctx.mark_non_differentiable(idx_kj, idx_ji)
-        ctx.set_materialize_grads(False)
-        return dist, angle, idx_kj, idx_ji
+    forward = staticmethod(_vec_geom_forward)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -290,14 +302,7 @@ class TripletVecGeomFn(torch.autograd.Function):
 class TripletVecGeom2Fn(torch.autograd.Function):
     """TripletVecGeomFn whose backward is recorded (TripletVecGeomBwdFn), so that d vec can be
     differentiated once more: energy-and-force training on a periodic structure."""
-
-    @staticmethod
-    def forward(ctx, vec, edge_index, num_nodes, shift_idx):
-        dist, angle, idx_kj, idx_ji = _run_pbc(vec, edge_index, num_nodes, shift_idx)
-        ctx.save_for_backward(vec, idx_kj, idx_ji)
-        ctx.mark_non_differentiable(idx_kj, idx_ji)
-        ctx.set_materialize_grads(False)
-        return dist, angle, idx_kj, idx_ji
+    forward = staticmethod(_vec_geom_forward)
 
     @staticmethod
     def backward(ctx, g_dist, g_angle, _g1, _g2):
@@ -328,8 +333,7 @@ class TripletVecGeomBwdFn(torch.autograd.Function):
         rows = torch.empty((2 * T + E, 3), dtype=torch.float32, device=dev)
         gg_d = torch.empty(E, dtype=torch.float32, device=dev)
         gg_a = torch.empty(T, dtype=torch.float32, device=dev)
-        gd = ops._f32c(g_dist) if g_dist is not None else None
-        ga = ops._f32c(g_angle) if g_angle is not None else None
+        gd, ga = _cot(g_dist), _cot(g_angle)
         ops.check(_lib.load().gmp_triplet_vec_bwd2_f32(
             ops._p(ops._f32c(vec)), E, ops._p(idx_kj), ops._p(idx_ji), T, ops._p(gd), ops._p(ga),
             ops._p(ops._f32c(a_vec)), ops._p(gg_d), ops._p(gg_a), ops._p(rows), ops._stream()),
@@ -388,9 +392,7 @@ class TripletVecDatFn(torch.autograd.Function):
             return None, None, None, None, None
         E, T = vec.shape[0], idx_kj.numel()
         rows = torch.empty((2 * T + E, 3), dtype=torch.float32, device=vec.device)
-        gd = ops._f32c(g_dist) if g_dist is not None else None
-        ga = ops._f32c(g_angle) if g_angle is not None else None
-        gt = ops._f32c(g_torsion) if g_torsion is not None else None
+        gd, ga, gt = _cot(g_dist), _cot(g_angle), _cot(g_torsion)
         ops.check(_lib.load().gmp_triplet_dat_vec_bwd_f32(
             ops._p(ops._f32c(vec)), E, ops._p(idx_kj), ops._p(idx_ji), ops._p(offs), ops._p(arg),
             T, ops._p(gd), ops._p(ga), ops._p(gt), ops._p(rows), ops._stream()),
@@ -408,6 +410,30 @@ def edge_vectors(pos, edge_index, shift):
     """vec (E, 3) = (pos[j] - pos[i]) + t, the K9p contract's featurised vector, in recorded ops
     (EdgePosDiffFn and an add: differentiable in pos and shift to any order)."""
     return ops.EdgePosDiffFn.apply(pos, ops._i64c(edge_index)) + shift
+
+
+def model_geometry_inputs(name, model, batch, first_order_only):
+    """The opening of a triplet model's forward: -> pos, shift, shift_idx for xyz_to_dat /
+    dimenet_angles.  A batch with edge_shift_idx needs model.periodic (NotImplementedError in the
+    model's `name`) and batch.cell (edge_shift's ValueError), both before any device work; with
+    first_order_only, pos and shift pass through FirstOrderOnlyFn (forces / stress yes, training
+    through them no)."""
+    shift_idx = getattr(batch, "edge_shift_idx", None)
+    shift = None
+    if shift_idx is not None:
+        if not getattr(model, "periodic", False):
+            raise NotImplementedError(
+                f"{name}: periodic shifts (edge_shift_idx) need a model built (or set) with "
+                "periodic=True: K11's open-boundary triplets take no periodic images")
+        shift = edge_shift(batch)
+    pos = batch.pos
+    ops._need_cuda(batch.atoms, pos, batch.edge_index, batch.batch)
+    if first_order_only and torch.is_grad_enabled():
+        if pos.requires_grad:
+            pos = ops.FirstOrderOnlyFn.apply(pos)
+        if shift is not None and shift.requires_grad:
+            shift = ops.FirstOrderOnlyFn.apply(shift)
+    return pos, shift, shift_idx
 
 
 def _geom_pbc(vec, edge_index, num_nodes, shift_idx, twice=False):

@@ -895,7 +895,9 @@ int gmp_triplet_geom_bwd2_f32(const float* pos, const int64_t* edge_index, int64
 /* Backward of the SphereNet torsion (spherenet_layer.py:535-559 under autograd) w.r.t. pos:
  * torsion_kn (T, from gmp_triplet_fill_f32; -1 = no candidate) is the scatter-min's winning
  * k_n, which alone receives the gradient (torch_scatter's arg routing).  Writes 4T rows of 3
- * floats and their node ids (i, j, k, k_n blocks of T); d pos = their segmented sum by node. */
+ * floats and their node ids (i, j, k, k_n blocks of T); d pos = their segmented sum by node.
+ * Zero rows without a candidate, for a zero cotangent, for an edge of zero length and where
+ * a^2 + b^2 == 0 (triplet or winner exactly collinear with the edge), where autograd gives NaN. */
 int gmp_triplet_torsion_bwd_f32(const float* pos, const int64_t* edge_index, int64_t n_edges,
                                 const int64_t* idx_kj, const int64_t* idx_ji,
                                 const int64_t* torsion_kn, int64_t n_triplets,
@@ -914,9 +916,12 @@ int gmp_triplet_torsion_bwd_f32(const float* pos, const int64_t* edge_index, int
  *          image of i and is kept; every entry that matches (a duplicated (j, i, S)) is excluded.
  *   order: edges in edge order (idx_ji non-decreasing); within an edge the order of the
  *          adjacency (ascending k, then ascending edge id; for a K9p graph ascending S).
- *   dist[e] = len3(vec_e): with all shifts zero bit-equal to K11's dist.
- *   angle[t] = atan2f(norm3(cross3(u, v)), dot3(u, v)), u = vec_ji, v = u + vec_kj (one rounded
- *          add per component; v is the image of k relative to i), the helpers those of K11.
+ *   dist[e] = dist_len3(vec_e) = sqrt(fma(y, y, x x) + z z): K11's dist, bit-equal to it with
+ *          all shifts zero.
+ *   angle[t] = atan2f(norm3(cross3(u, v)), dot3_sum(u, v)), u = vec_ji, v = u + vec_kj (one
+ *          rounded add per component; v is the image of k relative to i).  The helpers are those
+ *          of K11 (gmp_triplet_geom.h), each rounding explicit: dot3_sum rounds every product,
+ *          then ((+0 + xx) + yy) + zz; cross3 and norm3 are fma chains.
  *          With zero shifts the triplet lists equal K11's (mode 1) and the angle differs from
  *          its p_k - p_i form only by rounding.
  * Mode 1 (DimeNet, vertex i) only; no torsion.  adj_* as for K11.
@@ -925,24 +930,23 @@ int gmp_triplet_torsion_bwd_f32(const float* pos, const int64_t* edge_index, int
  *          that are the exclusive prefix sums of counts.
  * SphereNet (mode 0: angle at vertex j, and the torsion) on the same lists: idx_kj, idx_ji, dist
  * and the offsets are those of count / fill (angle = NULL), unchanged; gmp_triplet_dat_pbc_f32
- * adds, for triplet t of edge e, with the helpers of K11 and operation by operation as its
- * mode 0:
+ * adds, for triplet t of edge e, by the same device functions as K11's mode 0:
  *   vectors: u = sub3(0, vec_e) (a subtraction from +0, not a sign flip: an equal coordinate
  *          gives +0, as K11's p_i - p_j does), v = vec[idx_kj[t]].
- *   angle[t] = atan2f(norm3(cross3(u, v)), dot3(u, v)), at vertex j, in [0, pi].
+ *   angle[t] = atan2f(norm3(cross3(u, v)), dot3_sum(u, v)), at vertex j, in [0, pi].
  *   candidates of t: all triplets t' of the same edge, [offsets[e], offsets[e+1]), in index
  *          order, t' = t included (the same kept adjacency entries; in the open case the
  *          reference's "k_n != i", which keeps k_n = k); w = vec[idx_kj[t']].
- *   t1(t, t'): plane1 = cross3(u, v), plane2 = cross3(u, w), a = dot3(plane1, plane2),
- *          b = dot3(cross3(plane1, plane2), u) / len3(u) (a rounded division),
+ *   t1(t, t') = torsion_candidate: plane1 = cross3(u, v), plane2 = cross3(u, w),
+ *          a = dot3_sum(plane1, plane2), b = dot3_sum(cross3(plane1, plane2), u) / torsion_len3(u)
+ *          (a rounded division; torsion_len3(u) = sqrt(fma(x, x, y y) + z z)),
  *          t1 = atan2f(b, a), and t1 + 2 pi (a rounded addition) if t1 <= 0.
  *   torsion[t] = the minimum of t1 over the candidates by K11's rule: identity FLT_MAX, NaN
  *          never wins, 0 if nothing won.  torsion_arg[t] = the TRIPLET index t' of the first
  *          candidate among equal minima, -1 if none: the winning edge is
  *          idx_kj[torsion_arg[t]], and a duplicated (j, i, S) resolves to the lower index.
- * With all shifts zero this is K11's mode 0 bit for bit; for that, the sums of dot3 are kept
- * uncontracted and len3(u) of the torsion is evaluated as sqrt(fma(x, x, y y) + z z), which is
- * what K11's fill kernel does as compiled for gfx950 (pinned under fp contract(off)).
+ * With all shifts zero this is K11's mode 0 bit for bit: both kernels call the same helpers,
+ * whose roundings are stated under fp contract(off) and do not depend on the compiler.
  * ------------------------------------------------------------------------------------------ */
 int gmp_triplet_count_pbc(const float* vec, const int64_t* edge_index, int64_t n_edges,
                           int64_t n_nodes, const int64_t* adj_rowptr, const int64_t* adj_src,
@@ -984,8 +988,9 @@ int gmp_triplet_dat_pbc_f32(const float* vec, int64_t n_edges, const int64_t* id
  * edge whose winner torsion_arg is t (gathered in index order inside the kernel: no sort, no
  * atomics, a fixed order); [2T, 2T + E) grad_dist vec / d (written for n_triplets == 0 too).
  * The winner is held fixed (torch_scatter's arg routing); the 2 pi shift has unit derivative.
- * Zero rows for a zero cotangent and, for the torsion, where a^2 + b^2 == 0 or len3(u) == 0 (an
- * exactly collinear triplet, a candidate exactly parallel to u), where autograd gives NaN; the
+ * Zero rows for a zero cotangent and, for the torsion, where a^2 + b^2 == 0 or |u| == 0 (an
+ * exactly collinear triplet, a candidate exactly parallel to u), where autograd gives NaN (one
+ * torsion_bwd serves this kernel and K11's gmp_triplet_torsion_bwd_f32, same dead cases); the
  * angle's dead cases are those of gmp_triplet_vec_bwd_f32.  Any of the three cotangents may be
  * NULL (zero); offsets and torsion_arg are needed with grad_torsion only. */
 int gmp_triplet_dat_vec_bwd_f32(const float* vec, int64_t n_edges, const int64_t* idx_kj,

@@ -166,6 +166,50 @@ def test_torsion_backward_vs_oracle():
     assert torch.equal(g1, pd.grad)
 
 
+def test_torsion_backward_of_a_collinear_chain_is_zero():
+    """Four atoms exactly on a line: every triplet has plane1 == 0, so a = b = 0 for every
+    candidate and atan2 has no derivative there.  torsion_bwd's dead case writes zero rows (as
+    angle_bwd and K11p do), so d pos of the torsion alone is finite and exactly zero."""
+    from oracle.triplets import triplets as o_triplets
+    from gmp_amd.triplets import xyz_to_dat
+    pos = torch.tensor([[0., 0, 0], [1, 0, 0], [2, 0, 0], [3, 0, 0]])
+    d = torch.cdist(pos.double(), pos.double())
+    ei = torch.nonzero((d < 1.5) & (d > 0)).T.flip(0).contiguous()
+    idx_i, idx_j, idx_k = o_triplets(ei, 4)[:3]
+    plane1 = torch.cross(pos[idx_i] - pos[idx_j], pos[idx_k] - pos[idx_j], dim=-1)
+    assert plane1.dtype == torch.float32 and idx_i.numel() == 4 and bool((plane1 == 0).all())
+    pd = pos.to(DEV).requires_grad_(True)
+    out = xyz_to_dat(pd, ei.to(DEV), 4, use_torsion=True)
+    _check(out, o_xyz(pos, ei, 4, use_torsion=True), 3)
+    gt = torch.tensor([1.0, -2.0, 0.5, 3.0], device=DEV)
+    (out[2] * gt).sum().backward()
+    assert bool(torch.isfinite(pd.grad).all())
+    assert torch.equal(pd.grad, torch.zeros(4, 3, device=DEV))
+
+
+def test_fill_block_edge():
+    """257 directed edges, one past the fill kernel's block of 256: seed 671 makes edge 255 (the
+    last of block 0) empty and gives edge 256 (alone in block 1) triplets.  Lists equal the
+    oracle's, dist / angle / torsion within TOL, and the zero-shift periodic path gives the same
+    bits in all seven outputs."""
+    from gmp_amd.triplets import xyz_to_dat
+    n, E = 40, 257
+    pos, ei = _graph(n, 3.0, 1.2, 671)
+    assert ei.shape[1] >= E
+    ei = ei[:, :E].contiguous()
+    ref = o_xyz(pos, ei, n, use_torsion=True)
+    per_edge = torch.bincount(ref[6], minlength=E)
+    assert int(per_edge[255]) == 0 and int(per_edge[256]) >= 1
+    p, e = pos.to(DEV), ei.to(DEV)
+    out = xyz_to_dat(p, e, n, use_torsion=True)
+    _check(out, ref, 3)
+    pbc = xyz_to_dat(p, e, n, use_torsion=True, shift=torch.zeros(E, 3, device=DEV),
+                     shift_idx=torch.zeros(E, 3, dtype=torch.int32, device=DEV))
+    assert len(pbc) == len(out) == 7
+    for k, (a, b) in enumerate(zip(pbc, out)):
+        assert torch.equal(a, b), k
+
+
 def test_benchmark_size_properties():
     """50k nodes / ~1M edges: structural invariants + an fp64 spot check of angles."""
     from gmp_amd.graph import radius_graph
