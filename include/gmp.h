@@ -359,6 +359,16 @@ int gmp_edge_outer_sum_ex_f32(int64_t K, int64_t m, int64_t n, const float* A, i
  * (the module buffer, copied into the kernel arguments).  Any output pointer may be NULL.
  * Backward: g_vec (E,3) from g_sh / g_radial (either may be NULL); the caller scatters g_vec to
  * pos[ei0] (+) and pos[ei1] (-).
+ * Cutoff: an edge with len >= r_max (len == r_max included) gets a radial row of zeros (signed:
+ * -0.0 where the Bessel factor is negative, as the reference's product gives) and contributes
+ * exactly +0.0 to g_vec through g_radial; sh and its gradient do not depend on r_max.
+ * Zero-length edges (vec == 0: coincident nodes, or a self-loop (a, a)).  Forward, as the
+ * reference gives: sh = (1, 0, ..., 0), the radial row is NaN (sin(0) / 0), the GVP unit row is
+ * 0.  Backward: g_vec is exactly 0 from each of g_sh, g_radial and g_unit for finite cotangents
+ * (the reference's autograd returns NaN there).  The forward normalises with 1 / max(len, 1e-12)
+ * (F.normalize's eps) while the backward of sh is gated on len > 1e-12 and those of radial / unit
+ * on len > 0; vectors so short that len^2 underflows in fp32 (|vec| below about 1e-19) or that
+ * fall between the two gates are outside what the tests pin.
  * ------------------------------------------------------------------------------------------ */
 int gmp_edge_featurize_f32(const float* pos, const int64_t* edge_index, int64_t n_edges,
                            int num_bessel, const float* bessel_weights, float prefactor,
@@ -368,9 +378,12 @@ int gmp_edge_featurize_bwd_f32(const float* pos, const int64_t* edge_index, int6
                                int num_bessel, const float* bessel_weights, float prefactor,
                                float r_max, float p_cutoff, const float* g_sh,
                                const float* g_radial, float* g_vec, void* stream);
-/* The same for SphericalHarmonics(lmax) with 0 <= lmax <= 3 (max_ell of models/tfn.py:51 /
- * mace.py:25): sh rows of (lmax + 1)^2 floats, the l = 3 block being e3nn's component-
- * normalised sh_3_m (the lmax = 2 entries above are these with lmax = 2). */
+/* The same for SphericalHarmonics(lmax) with 0 <= lmax <= 5 (max_ell of models/tfn.py:51 /
+ * mace.py:25; anything else is GMP_ERR_ARG, as is num_bessel outside 0..32): sh rows of
+ * (lmax + 1)^2 floats, the l = 3 block being e3nn's component-normalised sh_3_m and the l = 4, 5
+ * blocks e3nn's CG recursion from it (the lmax = 2 entries above are these with lmax = 2).
+ * lmax = 0: sh == 1 and g_sh contributes exactly 0 to g_vec.  num_bessel = 0: no radial output
+ * is written and g_vec comes from g_sh alone. */
 int gmp_edge_featurize_lmax_f32(const float* pos, const int64_t* edge_index, int64_t n_edges,
                                 int lmax, int num_bessel, const float* bessel_weights,
                                 float prefactor, float r_max, float p_cutoff, float* vec_out,
